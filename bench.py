@@ -8,12 +8,16 @@ as [online Hadamard +] static int8 quantize -> int8 x int4 MFMA GEMM with fused 
 inputs resident in HBM.  Attention, norms, RoPE and lm_head are outside the path (SURVEY.md
 section 8) and are not executed.  Weights are random with the real shapes; data is synthetic.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR: what the last timed step returned (the last Linear's output, the logits) as DIR/<name>.npy, float32.
+--full: also the measurements and checks beyond the headline figure -- kernel attribution and roofline (sustained int8
+peak, floor model), whole-prefill TTFT, CPU baselines, the secondary configurations, the multi-rank logits checks.
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (the driver's command) the
 process is a rank; started plainly with --gpus N it spawns the N ranks itself as FRESH child
 processes (before anything touches the GPU) and returns their exit code.  Every rank prefills its
 own image+prompt sample (batch sharding, sample i -> rank i % N, weak scaling); the ranks exchange
-their real last-token logits with one RCCL all_gather per step, and rank 0 checks the gathered
+their real last-token logits with one RCCL all_gather per step, and (--full) rank 0 checks the gathered
 logits against its own single-GPU computation of every sample.  Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -267,7 +271,7 @@ def run_secondary(budget_s: float, t_start: float, steps: int = 10, warmup: int 
         if left < 30.0:
             out[name] = {"what": what, "skipped": f"time budget spent ({budget_s:.0f} s for the whole bench)"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline",
                "--no-secondary"] + (["--no-full-prefill"] if "--ttft-kv-fp8" not in extra else []) + extra
         t0 = time.perf_counter()
         try:
@@ -371,7 +375,16 @@ def main():
                     help="image+prompt samples per GPU and step (the benchmark configuration is 1; >1 is a scaling study)")
     ap.add_argument("--cpu-selftest", action="store_true",
                     help="launcher / sharding self-test without a GPU: the ranks gather fake logits over gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: kernel attribution and roofline (sustained int8 "
+                         "peak, floor model), whole-prefill TTFT, CPU baselines, the secondary configurations, the multi-rank logits "
+                         "checks (the --no-* options above switch single parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the last Linear's output, the logits) "
+                         "as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     t_process = time.perf_counter()
 
     # ---- rank launcher: before torch.cuda / HIP is touched, and never by re-exec ---------------------
@@ -464,7 +477,7 @@ def main():
     # N > 1: sample i runs on rank i; static scales are replicated constants (every rank calibrates on
     # sample 0 with the same seeds).  The whole-prefill logits of this rank's sample, for the parity check:
     fp_logits, logits_local = None, None
-    if distributed and headline and args.batch == 1 and not args.no_fuse:
+    if args.full and distributed and headline and args.batch == 1 and not args.no_fuse:
         from mquant_amd.full_prefill import FullPrefill
         fp_logits = FullPrefill(pf, fused_glue=True)
         fp_logits.calibrate()
@@ -513,7 +526,8 @@ def main():
             lm_logits(h)
         return y
 
-    run_step = capture(hot_path_and_logits)
+    step_out = [None]                    # the last Linear's output of the latest step (the graph's own buffer when captured)
+    run_step = capture(hot_path_and_logits, step_out)
     counter = [0]
     side_done = [None, None]
 
@@ -560,8 +574,20 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * tokens_per_step * args.steps / elapsed
 
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step, before anything else runs on the model
+        import numpy as np
+        outputs = {"last_linear_out": step_out[0]}
+        if with_logits:
+            outputs["logits"] = logits_step
+            if distributed:
+                outputs["logits_all_ranks"] = logits_all[(counter[0] - 1) & 1]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.float().cpu().numpy())
+
     logits_check = None
-    if distributed and with_logits:
+    if args.full and distributed and with_logits:
         # what the timed steps exchanged: row r of the gathered tensor is rank r's logits of that step
         par = (counter[0] - 1) & 1
         mine = logits_all[par][rank * B_local:(rank + 1) * B_local]
@@ -592,116 +618,117 @@ def main():
             fp_logits.restore_hot_path_scales()
             logits_check = dict(logits_check or {}, samples=world, equal_to_single_gpu=all(same), per_sample=same)
 
-    # ---- kernel attribution: the GEMM launches of a step alone, HIP events on the launch stream
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = max(3, min(args.steps, 10))
+    if args.full:
+        # ---- kernel attribution: the GEMM launches of a step alone, HIP events on the launch stream
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = max(3, min(args.steps, 10))
 
-    def timed(run, batches=5):
-        """average duration of one replay: median over ``batches`` batches of ``reps`` back-to-back replays (a single
-        batch right after the host-side checks above was seen 13 % slow on a fresh box: clocks / power state)"""
-        for _ in range(2):
-            run()
-        torch.cuda.synchronize(dev)
-        got = []
-        for _ in range(batches):
-            e0.record()
-            for _ in range(reps):
+        def timed(run, batches=5):
+            """average duration of one replay: median over ``batches`` batches of ``reps`` back-to-back replays (a single
+            batch right after the host-side checks above was seen 13 % slow on a fresh box: clocks / power state)"""
+            for _ in range(2):
                 run()
-            e1.record()
             torch.cuda.synchronize(dev)
-            got.append(e0.elapsed_time(e1) / reps)
-        got.sort()
-        return got[len(got) // 2]
+            got = []
+            for _ in range(batches):
+                e0.record()
+                for _ in range(reps):
+                    run()
+                e1.record()
+                torch.cuda.synchronize(dev)
+                got.append(e0.elapsed_time(e1) / reps)
+            got.sort()
+            return got[len(got) // 2]
 
-    hot_ms = timed(capture(pf.step))                 # the hot path alone (no logits, no exchange), stream-timed
-    gemm_ms = timed(capture(pf.step_gemm_only))
-    quant_ms = timed(capture(pf.step_quant_only))
-    lm_ms = None
-    if with_logits:
-        last_row = torch.zeros((B_local, hidden), dtype=torch.float16, device=dev)
+        hot_ms = timed(capture(pf.step))                 # the hot path alone (no logits, no exchange), stream-timed
+        gemm_ms = timed(capture(pf.step_gemm_only))
+        quant_ms = timed(capture(pf.step_quant_only))
+        lm_ms = None
+        if with_logits:
+            last_row = torch.zeros((B_local, hidden), dtype=torch.float16, device=dev)
 
-        def lm_only():
-            h = torch.nn.functional.rms_norm(last_row, (hidden,), eps=1e-6)
-            lm_logits(h)
-        lm_ms = timed(lm_only)
-    launches = pf.gemm_launches()
-    traffic, traffic_note, traffic_source, traffic_stale = None, "no PMC traffic file for this workload", None, None
-    tpath = next((pth for pth in (os.path.join(ROOT, "profiles", nm) for nm in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json", "r2_traffic.json"))
-                  if os.path.exists(pth)), None)
-    if tpath and headline and args.batch == 1 and not args.no_fuse:
-        # HBM bytes per GEMM launch from the PMC passes (tools/pmc_traffic.py); counters cannot be
-        # read inside the timed run, so this is the committed measurement of the same command -- with
-        # the commit and command it was taken at, so that a stale file is detectable
-        with open(tpath) as fh:
-            tj = json.load(fh)
-        traffic = tj["kernels"].get("gemm", {}).get("hbm_bytes_per_launch")
-        traffic_note = tj["corrections"]
-        # stale = any kernel source changed since the counters were taken (digest over mquant_amd/csrc/*.hip, *.h recorded by
-        # tools/pmc_traffic.py; files measured before round 4 carry none and count as stale)
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        try:
-            from pmc_traffic import csrc_digest
-            digest_now = csrc_digest()
-        except Exception:
-            digest_now = None
-        traffic_stale = not (digest_now is not None and tj.get("csrc_sha16") == digest_now)
-        traffic_source = {"file": os.path.relpath(tpath, ROOT), "measured_at_commit": tj.get("commit"),
-                          "command": tj.get("command"), "csrc_sha16": tj.get("csrc_sha16"), "csrc_sha16_now": digest_now}
-    achieved = pf.gemm_ops() / (gemm_ms * 1e-3) / 1e12
-    step_tops = pf.gemm_ops() / (ms_per_step * 1e-3) / 1e12
-    roofline = {"bound": "mfma", "kernel": "gemm_ws_kernel / gemm_w4a8_pp_kernel 256x256 (both V_MFMA_I32_16X16X64_I8)",
-                "achieved": round(achieved, 2), "peak": PEAK_INT8_TOPS, "unit": "TOP/s",
-                "frac": round(achieved / PEAK_INT8_TOPS, 4),
-                "step_frac": round(step_tops / PEAK_INT8_TOPS, 4),
-                "step_frac_note": "GEMM ops / ms_per_step / peak: the whole timed step (quantize and Hadamard launches included), "
-                                  "where frac covers the GEMM launches alone",
-                "traffic": traffic,
-                "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)", "traffic_note": traffic_note,
-                "traffic_source": traffic_source, "traffic_stale": traffic_stale,
-                "algorithmic_bytes_per_launch": round(pf.gemm_bytes() / launches),
-                "launches_per_step": launches,
-                "avg_launch_us": round(gemm_ms * 1e3 / launches, 3),
-                "algorithmic_ops_per_launch": round(pf.gemm_ops() / launches),
-                "gemm_ms_per_step": round(gemm_ms, 4),
-                "quant_hadamard_ms_per_step": round(quant_ms, 4),
-                "quant_hadamard_GBps": round(pf.quant_bytes() / (quant_ms * 1e-3) / 1e9, 1),
-                "hot_path_ms_per_step_stream_timed": round(hot_ms, 4)}
+            def lm_only():
+                h = torch.nn.functional.rms_norm(last_row, (hidden,), eps=1e-6)
+                lm_logits(h)
+            lm_ms = timed(lm_only)
+        launches = pf.gemm_launches()
+        traffic, traffic_note, traffic_source, traffic_stale = None, "no PMC traffic file for this workload", None, None
+        tpath = next((pth for pth in (os.path.join(ROOT, "profiles", nm) for nm in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json", "r2_traffic.json"))
+                      if os.path.exists(pth)), None)
+        if tpath and headline and args.batch == 1 and not args.no_fuse:
+            # HBM bytes per GEMM launch from the PMC passes (tools/pmc_traffic.py); counters cannot be
+            # read inside the timed run, so this is the committed measurement of the same command -- with
+            # the commit and command it was taken at, so that a stale file is detectable
+            with open(tpath) as fh:
+                tj = json.load(fh)
+            traffic = tj["kernels"].get("gemm", {}).get("hbm_bytes_per_launch")
+            traffic_note = tj["corrections"]
+            # stale = any kernel source changed since the counters were taken (digest over mquant_amd/csrc/*.hip, *.h recorded by
+            # tools/pmc_traffic.py; files measured before round 4 carry none and count as stale)
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            try:
+                from pmc_traffic import csrc_digest
+                digest_now = csrc_digest()
+            except Exception:
+                digest_now = None
+            traffic_stale = not (digest_now is not None and tj.get("csrc_sha16") == digest_now)
+            traffic_source = {"file": os.path.relpath(tpath, ROOT), "measured_at_commit": tj.get("commit"),
+                              "command": tj.get("command"), "csrc_sha16": tj.get("csrc_sha16"), "csrc_sha16_now": digest_now}
+        achieved = pf.gemm_ops() / (gemm_ms * 1e-3) / 1e12
+        step_tops = pf.gemm_ops() / (ms_per_step * 1e-3) / 1e12
+        roofline = {"bound": "mfma", "kernel": "gemm_ws_kernel / gemm_w4a8_pp_kernel 256x256 (both V_MFMA_I32_16X16X64_I8)",
+                    "achieved": round(achieved, 2), "peak": PEAK_INT8_TOPS, "unit": "TOP/s",
+                    "frac": round(achieved / PEAK_INT8_TOPS, 4),
+                    "step_frac": round(step_tops / PEAK_INT8_TOPS, 4),
+                    "step_frac_note": "GEMM ops / ms_per_step / peak: the whole timed step (quantize and Hadamard launches included), "
+                                      "where frac covers the GEMM launches alone",
+                    "traffic": traffic,
+                    "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)", "traffic_note": traffic_note,
+                    "traffic_source": traffic_source, "traffic_stale": traffic_stale,
+                    "algorithmic_bytes_per_launch": round(pf.gemm_bytes() / launches),
+                    "launches_per_step": launches,
+                    "avg_launch_us": round(gemm_ms * 1e3 / launches, 3),
+                    "algorithmic_ops_per_launch": round(pf.gemm_ops() / launches),
+                    "gemm_ms_per_step": round(gemm_ms, 4),
+                    "quant_hadamard_ms_per_step": round(quant_ms, 4),
+                    "quant_hadamard_GBps": round(pf.quant_bytes() / (quant_ms * 1e-3) / 1e9, 1),
+                    "hot_path_ms_per_step_stream_timed": round(hot_ms, 4)}
 
-    if not args.tiny:
-        try:
-            sus = sustained_int8_peak(pf, dev)
-            top = max(sus["mfma_i32_16x16x64_i8"], sus["mfma_i32_32x32x32_i8"])
-            roofline["peak_sustained_measured"] = {
-                "value": top, "unit": "TOP/s", "by_instruction": sus,
-                "how": "mq_bench_mfma_burn: register-only int8 MFMA chains, 2 waves per SIMD on every CU, no memory traffic, operand bytes "
-                       "taken from this workload's int8 activations and unpacked int4 weights; ~60 ms per reading, measured live on this box",
-                "frac_of_sustained": round(achieved / top, 4), "step_frac_of_sustained": round(step_tops / top, 4),
-                "note": "the package power limit (~1.3-1.4 kW) sets the clock: the nominal peak (2.4 GHz) is reached on all-zero operands only; "
-                        "frac keeps the nominal peak as its denominator (profiles/r5_clock_reconciliation.txt)"}
-        except Exception as exc:  # a report, never a reason to lose the line
-            roofline["peak_sustained_measured"] = {"value": None, "how": f"failed: {exc!r}"}
+        if not args.tiny:
+            try:
+                sus = sustained_int8_peak(pf, dev)
+                top = max(sus["mfma_i32_16x16x64_i8"], sus["mfma_i32_32x32x32_i8"])
+                roofline["peak_sustained_measured"] = {
+                    "value": top, "unit": "TOP/s", "by_instruction": sus,
+                    "how": "mq_bench_mfma_burn: register-only int8 MFMA chains, 2 waves per SIMD on every CU, no memory traffic, operand bytes "
+                           "taken from this workload's int8 activations and unpacked int4 weights; ~60 ms per reading, measured live on this box",
+                    "frac_of_sustained": round(achieved / top, 4), "step_frac_of_sustained": round(step_tops / top, 4),
+                    "note": "the package power limit (~1.3-1.4 kW) sets the clock: the nominal peak (2.4 GHz) is reached on all-zero operands only; "
+                            "frac keeps the nominal peak as its denominator (profiles/r5_clock_reconciliation.txt)"}
+            except Exception as exc:  # a report, never a reason to lose the line
+                roofline["peak_sustained_measured"] = {"value": None, "how": f"failed: {exc!r}"}
 
-    if not args.tiny and not args.no_floor_model:
-        # per-shape launch times (each shape's GEMMs back to back from their own hipGraph, distinct weight images as in the step) and the
-        # floor model beside them: mquant_amd/floor_model.py
-        try:
-            from mquant_amd import floor_model
-            from mquant_amd.engine import WORKSPACE
-            groups = floor_model.shape_groups(pf.layers)
-            per_shape_us = {}
-            for gi, grp in enumerate(groups):
-                def run_group(grp=grp):
-                    for L in grp["layers"]:
-                        a = WORKSPACE.act(dev, L.spec.M, L.lin.K_pad)
-                        x0 = WORKSPACE.x0(dev, L.spec.M) if L.lin.split else None
-                        L.lin.gemm(a, x0, torch.float16, L.row_sel, L.out)
-                per_shape_us[gi] = timed(capture(run_group), batches=3) * 1e3 / len(grp["layers"])
-            sus_top = (roofline.get("peak_sustained_measured") or {}).get("value") or 0.0
-            fm = floor_model.summarize(groups, per_shape_us, sus_top, cus=torch.cuda.get_device_properties(dev).multi_processor_count)
-            roofline["frac_floor_model"] = fm["frac_floor_model"]
-            roofline["floor_model"] = fm
-        except Exception as exc:  # a report, never a reason to lose the line
-            roofline["floor_model"] = {"error": repr(exc)}
+        if not args.tiny and not args.no_floor_model:
+            # per-shape launch times (each shape's GEMMs back to back from their own hipGraph, distinct weight images as in the step) and the
+            # floor model beside them: mquant_amd/floor_model.py
+            try:
+                from mquant_amd import floor_model
+                from mquant_amd.engine import WORKSPACE
+                groups = floor_model.shape_groups(pf.layers)
+                per_shape_us = {}
+                for gi, grp in enumerate(groups):
+                    def run_group(grp=grp):
+                        for L in grp["layers"]:
+                            a = WORKSPACE.act(dev, L.spec.M, L.lin.K_pad)
+                            x0 = WORKSPACE.x0(dev, L.spec.M) if L.lin.split else None
+                            L.lin.gemm(a, x0, torch.float16, L.row_sel, L.out)
+                    per_shape_us[gi] = timed(capture(run_group), batches=3) * 1e3 / len(grp["layers"])
+                sus_top = (roofline.get("peak_sustained_measured") or {}).get("value") or 0.0
+                fm = floor_model.summarize(groups, per_shape_us, sus_top, cus=torch.cuda.get_device_properties(dev).multi_processor_count)
+                roofline["frac_floor_model"] = fm["frac_floor_model"]
+                roofline["floor_model"] = fm
+            except Exception as exc:  # a report, never a reason to lose the line
+                roofline["floor_model"] = {"error": repr(exc)}
 
     n_lin = sum(sp.count for sp in specs)
     desc = workload_desc + f", M_llm={workload.M_LLM}"
@@ -737,14 +764,14 @@ def main():
                                   + ("; the RCCL all_gather of the ranks' logits runs on a side stream and overlaps the next sample's hot path" if distributed else "")
                                   if with_logits else ""),
                        "tokens_per_step_per_gpu": tokens_per_step, "parallelism": f"batch-shard x{world}",
-                       "ttft_hot_path_ms": round(hot_ms, 4),
-                       "lm_head_ms": None if lm_ms is None else round(lm_ms, 4),
                        "gemm_TOP_per_step": round(pf.gemm_ops() / 1e12, 3),
                        "hip_graph": not args.no_graph, "settle_replays": settle_replays,
                        "settle_replays_note": "untimed replays of the captured step before the contract's warm-up steps",
-                       "weights_GB": round(pf.weight_bytes() / 1e9, 3)},
-            "roofline": roofline}
-    if headline and not (args.no_full_prefill or args.no_fuse or args.batch != 1):
+                       "weights_GB": round(pf.weight_bytes() / 1e9, 3)}}
+    if args.full:
+        line["config"].update(ttft_hot_path_ms=round(hot_ms, 4), lm_head_ms=None if lm_ms is None else round(lm_ms, 4))
+        line["roofline"] = roofline
+    if args.full and headline and not (args.no_full_prefill or args.no_fuse or args.batch != 1):
         line["full_prefill"] = full_prefill_report(pf, dev, args)
     if args.ttft_kv_fp8 and not args.tiny and args.workload in ("qwen2vl_7b", "qwen2vl_72b") and not args.no_fuse and args.batch == 1:
         from mquant_amd import full_prefill as fpm
@@ -755,7 +782,7 @@ def main():
                                            "rank): ran as a single process")
     if logits_check is not None:
         line["logits_check"] = logits_check
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
         try:
             line["cpu_baseline"] = cpu_baseline_reference()
         except Exception as exc:  # the baseline is a report, never a reason to lose the line
@@ -765,7 +792,7 @@ def main():
             line["cpu_baseline_port"] = cpu_baseline(float(pf.gemm_ops()))
         except Exception as exc:
             line["cpu_baseline_port"] = {"value": None, "kind": "port", "sample": f"failed: {exc!r}"}
-    if rank == 0 and world == 1 and headline and not args.no_secondary and not args.no_fuse and args.batch == 1 and not args.had_fast:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_secondary and not args.no_fuse and args.batch == 1 and not args.had_fast:
         # the headline is complete; the other configurations follow as bounded child processes (this process keeps its line)
         try:
             pf = None

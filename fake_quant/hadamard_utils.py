@@ -129,6 +129,13 @@ def _butterflies(x: torch.Tensor, m: int) -> torch.Tensor:
     return y.reshape(shape)
 
 
+def _sqrt_f32(n: int) -> torch.Tensor:
+    """sqrt(n) correctly rounded to fp32: what the reference's ``torch.tensor(n).sqrt()`` gave for the goldens' widths.  That
+    integer-tensor sqrt is an ulp off for some n, and which n depends on the CPU (n = 11008 on some); the double sqrt
+    rounded to fp32 is exact for every n."""
+    return torch.tensor(math.sqrt(n), dtype=torch.float32)
+
+
 def matmul_hadU(X: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     n = X.shape[-1]
     hadK, K = get_hadK(n, transpose)
@@ -136,7 +143,7 @@ def matmul_hadU(X: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     y = _butterflies(X.clone(), m)
     if K > 1:
         y = (hadK.to(device=y.device, dtype=y.dtype) @ y.reshape(-1, K, m)).reshape(X.shape)
-    return y / torch.tensor(n).sqrt()
+    return y / _sqrt_f32(n)
 
 
 def matmul_hadUt(X: torch.Tensor) -> torch.Tensor:
@@ -173,7 +180,7 @@ def _hadamard_torch(X: torch.Tensor, hadK, K: int) -> torch.Tensor:
     Offline weight surgery on CPU / fp64 tensors only -- never the online path."""
     n = X.shape[-1]
     m = n // K
-    scale = 1.0 / torch.tensor(n).sqrt()
+    scale = 1.0 / _sqrt_f32(n)
     y = _butterflies(X.float() if X.dtype in (torch.float16, torch.bfloat16) else X.clone(), m)
     y = (y * scale.to(y.dtype)).to(X.dtype)
     if K > 1:

@@ -45,6 +45,12 @@ def test_a_stray_world_size_without_the_rendezvous_environment_runs_as_a_single_
     assert line["n_gpus"] == 1 and line["gathered_ok"] is True
 
 
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: zero of them has no time per step and is refused before any work."""
+    r = _run(["--steps", "0", "--cpu-selftest"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_launcher_runs_before_any_gpu_import():
     """The spawn decision sits above every torch import of main(): the parent must never initialise HIP."""
     src = open(BENCH).read()

@@ -22,7 +22,7 @@ def test_bench_two_ranks_gather_the_single_gpu_logits():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-full-prefill"], env=env, capture_output=True, text=True, timeout=1800)
+                        "--full", "--no-cpu-baseline", "--no-full-prefill"], env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2
@@ -76,7 +76,7 @@ def test_bench_as_a_single_torchrun_rank_initialises_rccl_and_exchanges_logits_o
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-full-prefill"]
+           "--full", "--no-cpu-baseline", "--no-full-prefill"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -101,7 +101,7 @@ def test_bench_single_torchrun_rank_with_four_samples_per_gpu_on_internvl2():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "4", "--workload", "internvl2_8b", "--no-cpu-baseline", "--no-full-prefill"]
+           "--batch", "4", "--workload", "internvl2_8b", "--full", "--no-cpu-baseline", "--no-full-prefill"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

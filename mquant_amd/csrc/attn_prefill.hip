@@ -7,7 +7,8 @@
 //   * mq_attn_prefill_quant_i8: either of them with the NEXT Linear's static int8 activation quantizer fused into the store.
 // The reference has neither a KV-cache quantizer nor an attention kernel of its own (fake_quant/utils.py:220-267 are flags
 // of an unused parser; attention is HF model code): PARITY UNPINNED -- the checker is float64 softmax attention (over the
-// dequantised cache for the e4m3 variant), restated in tests/test_gpu_attn_prefill.py.
+// dequantised cache for the e4m3 variant) with a bound for every output element derived from the roundings below,
+// tests/attn_reference.py.
 //
 //     S[q][k] = (sum_d Q[q][d] * K8[k][d]) * s_k[kvh] * softmax_scale        (causal: k <= q)
 //     O[q][d] = (sum_k softmax_k(S)[q][k] * V8[k][d]) * s_v[kvh]

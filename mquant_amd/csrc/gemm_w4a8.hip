@@ -801,6 +801,9 @@ static int gemm_common(const int8_t *a, long lda, const void *w, int w_bits, lon
         const long n_out = act == MQ_ACT_SILU_MUL ? N / 2 : N;
         MQ_REQUIRE(act != MQ_ACT_SILU_MUL || N % 64 == 0, "mq_gemm_w4a8_act_ws: silu(gate)*up needs N = 2 x (a multiple of 32) channels, gate then up (N = %ld)", N);
         MQ_REQUIRE(n_out % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out) % 16 == 0, "mq_gemm_w4a8_act_ws: output columns and ldo must be multiples of 8, out 16-byte aligned");
+        // (every form of the activation epilogue reads s_w and bias 16 bytes at a time, gemm_common.h: a view at a 4-byte offset -- a slice
+        //  of a fused parameter tensor -- is refused here rather than handed to unaligned 16-byte loads)
+        MQ_REQUIRE(((uintptr_t)s_w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0, "mq_gemm_w4a8_act_ws: s_w and bias must be 16-byte aligned");
         p.act = act;
     }
     const bool rope = rope_cos != nullptr;

@@ -301,7 +301,7 @@ class W4A8Linear:
         """Whether ``gemm_act`` can run this layer: a plain static layer (no split column, rank-1 terms, groups or --act_order), tiled
         activations, and for silu(gate) * up a fused gate|up image of 2 x (a multiple of 32) channels."""
         plain = (not self.split and self.w_shift is None and self.w_groups is None and self.dynamic is None and self.col_perm is None
-                 and ACT_LAYOUT == "tiled")
+                 and ACT_LAYOUT == "tiled" and self.s_w.data_ptr() % 16 == 0 and (self.bias is None or self.bias.data_ptr() % 16 == 0))
         if act == ops.ACT_SILU_MUL:
             return plain and self.N % 64 == 0
         return plain and act == ops.ACT_QUICK_GELU and self.N % 8 == 0

@@ -1,5 +1,5 @@
-// gemm_common.h -- pieces shared by the W4A8 GEMM kernels (gemm_w4a8.hip, gemm_ws.hip):
-// argument block, LDS-DMA helper, dequantisation epilogue.
+// gemm_common.h -- pieces shared by the W4A8 GEMM kernels (gemm_w4a8.hip, gemm_ws.hip, gemm_pp.hip, gemm_skinny.hip):
+// argument block, tile ids, LDS-DMA helper, dequantisation epilogue.
 #pragma once
 #include <type_traits>
 
@@ -138,6 +138,67 @@ inline bool geometry_in_range(const GemmArgs &p)
     unsigned long long d = p.mg > p.n_blocks ? p.mg : p.n_blocks;
     if (p.xm > d) d = p.xm;
     return total * d < (1ULL << 32) && total < (1ULL << 31);
+}
+
+// Tile ids: what Plan::tile holds and what the tests, the tools and mq_gemm_debug_force pass as plain numbers (so the values are fixed).
+// Rows x channels of a workgroup's output tile; an id that is in no list takes the symmetric 128 x 128 kernel with 2 x 2 waves.
+enum TileId : int {
+    // gemm_w4a8.hip, the symmetric kernel (every wave loads and multiplies; row-major or tiled activations), wave grid in brackets
+    TILE_SYM_256x256_8W = 1,    // [2 x 4]; int8 weights: 256 x 128 [4 x 2] (3 x 64 KiB of stages would not fit)
+    TILE_SYM_256x128 = 2,       // [4 x 2]
+    TILE_SYM_256x256 = 3,       // [4 x 4], 16 waves; int8 weights: 256 x 128 [4 x 2]
+    TILE_SYM_128x256 = 4,       // [2 x 4]
+    TILE_SYM_256x128_2x4 = 5,   // [2 x 4]
+    TILE_SYM_64x128 = 10,       // [2 x 2]
+    TILE_SYM_128x64 = 11,       // [2 x 2]
+    TILE_SYM_128x128_4x2 = 12,  // [4 x 2]
+    TILE_PIPE_256x256 = 13,     // the software-pipelined 16-wave kernel of rounds 1-3 (W4)
+    TILE_SYM_128x128 = 26,      // [2 x 4]; also the round-1 kernel of the group-scale paths
+    TILE_SYM_96x128 = 31,       // [1 x 4]
+    TILE_SYM_192x128 = 35,      // [2 x 4], W4
+    // gemm_pp.hip, the 8-wave ping-pong kernels (W4, tiled activations)
+    TILE_PP_256x256 = 14,
+    TILE_PP_128x128 = 15,
+    TILE_PP_96x128 = 16,
+    TILE_PP_192x128 = 17,
+    TILE_PP_64x128 = 18,
+    TILE_PP_128x256 = 19,
+    TILE_PP_256x256_DIRECT = 20,  // 14 with the slab-free epilogue and the next tile's stages requested ahead
+    // gemm_ws.hip, the wave-specialised kernels (tiled activations): four loader waves, one math wave per SIMD or two
+    TILE_WS_FIRST = 40, TILE_WS_END = 60,   // (the range kept for them)
+    TILE_WS32_96x128 = 40,      // V_MFMA_I32_32X32X32_I8 in the math waves (round 2)
+    TILE_WS32_128x128 = 41,
+    TILE_WS32_192x128 = 42,     // W4
+    TILE_WS32_64x128 = 43,
+    TILE_WS_96x128 = 44,        // the same tiles with V_MFMA_I32_16X16X64_I8 (round 5)
+    TILE_WS_128x128 = 45,
+    TILE_WS_192x128 = 46,       // W4
+    TILE_WS_64x128 = 47,
+    TILE_WS_96x128_2W = 48,     // 96 x 128 with TWO math waves per SIMD (48 x 32 per wave)
+    TILE_WSD_96x128 = 50,       // 44-48 with the slab-free (DIRECT) epilogue (round 6)
+    TILE_WSD_128x128 = 51,
+    TILE_WSD_192x128 = 52,      // W4
+    TILE_WSD_64x128 = 53,
+    TILE_WSD_96x128_2W = 54,
+    // gemm_skinny.hip, the weight-streaming kernels for a few rows (W4, tiled activations); Plan::splits = their K slices
+    TILE_SKINNY = 60,           // up to four row tiles: a wave per channel pair and slice
+    TILE_SKINNY_WG = 61,        // up to two row tiles: a workgroup per channel pair, its eight waves (and grid.y) are the slices
+};
+constexpr bool tile_is_ws(int t) { return t >= TILE_WS_FIRST && t < TILE_WS_END; }
+constexpr bool tile_is_pp(int t) { return t >= TILE_PP_256x256 && t <= TILE_PP_256x256_DIRECT; }
+constexpr bool tile_is_skinny(int t) { return t == TILE_SKINNY || t == TILE_SKINNY_WG; }
+constexpr bool tile_is_ws_direct(int t) { return t >= TILE_WSD_96x128 && t <= TILE_WSD_96x128_2W; }
+// GemmArgs::act in the store: every wave-specialised tile and the 256-wide ping-pong tiles (launch_gemm_pp / dispatch_ws_act hold the kernels)
+constexpr bool tile_has_act(int t) { return tile_is_ws(t) || t == TILE_PP_256x256 || t == TILE_PP_128x256 || t == TILE_PP_256x256_DIRECT; }
+// the tile with the LDS slab that a slab-free id falls back to when a launch is not covered (any other id: itself)
+constexpr int tile_slab_twin(int t) { return tile_is_ws_direct(t) ? t - 6 : (t == TILE_PP_256x256_DIRECT ? (int)TILE_PP_256x256 : t); }
+
+// What every slab-free (DIRECT) epilogue needs of a launch: a 16-bit output it can store 16 bytes at a time and parameters it can read 16
+// bytes at a time.  The callers add what differs between them (split-K, residual, second rank-1 term, RoPE, float accumulators).
+template <int EPI>
+inline bool direct_epilogue_ok(const GemmArgs &p)
+{
+    return (EPI == EPI_F16 || EPI == EPI_BF16) && p.vec_ok && p.par_ok && ((uintptr_t)p.s_w) % 16 == 0;
 }
 
 // Kernel arguments up front.  hipcc loads a by-value argument block lazily, field by field next to its first use, with an

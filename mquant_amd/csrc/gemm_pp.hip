@@ -414,7 +414,7 @@ static int launch_pp(const GemmArgs &p, hipStream_t st)
 // test hook (mq_gemm_debug_force bit 16 of `splits`): keep the slab form of the activation epilogue (A/B, tile sweeps)
 thread_local int g_pp_act_slab = 0;
 
-// tile ids 14 (256 x 256), 15 (128 x 128), 16 (96 x 128), 17 (192 x 128), 18 (64 x 128), 19 (128 x 256), 20 (256 x 256, slab-free epilogue)
+// the TILE_PP_* ids of gemm_common.h
 template <int EPI>
 int launch_gemm_pp(const GemmArgs &p, int tile, hipStream_t st)
 {
@@ -423,32 +423,31 @@ int launch_gemm_pp(const GemmArgs &p, int tile, hipStream_t st)
         // gate pair AND its up pair (the plan sends every other shape to the wave-specialised kernels)
         if constexpr (EPI == EPI_F16 || EPI == EPI_BF16) {
             // silu(gate) * up without the slab (both operands of an output sit in one lane of the D layout), next tile primed
-            if ((tile == 14 || tile == 20) && p.act == MQ_ACT_SILU_MUL && ((uintptr_t)p.s_w) % 16 == 0 && (!p.bias || ((uintptr_t)p.bias) % 16 == 0)
+            if (tile_slab_twin(tile) == TILE_PP_256x256 && p.act == MQ_ACT_SILU_MUL && ((uintptr_t)p.s_w) % 16 == 0 && (!p.bias || ((uintptr_t)p.bias) % 16 == 0)
                 && g_pp_act_slab == 0)
                 return launch_pp<256, 256, 1, 6, EPI, true, true>(p, st);
         }
         if constexpr (EPI != EPI_I32) {
-            if (tile == 14 || tile == 20) return launch_pp<256, 256, 1, 6, EPI, true>(p, st);
-            if (tile == 19) return launch_pp<128, 256, 1, 8, EPI, true>(p, st);
+            if (tile_slab_twin(tile) == TILE_PP_256x256) return launch_pp<256, 256, 1, 6, EPI, true>(p, st);
+            if (tile == TILE_PP_128x256) return launch_pp<128, 256, 1, 8, EPI, true>(p, st);
         }
         return fail(MQ_EINVAL, "gemm_pp: tile %d has no activation epilogue", tile);
     }
-    if (tile == 20) {
-        // the 256 x 256 tile with the slab-free epilogue: plain 16-bit launches only, anything else takes tile 14
-        const bool direct_ok = (EPI == EPI_F16 || EPI == EPI_BF16) && p.splits == 1 && !p.residual && !p.x1 && !p.acc_float && p.vec_ok && p.par_ok
-                               && ((uintptr_t)p.s_w) % 16 == 0;
+    if (tile == TILE_PP_256x256_DIRECT) {
+        // the 256 x 256 tile with the slab-free epilogue: plain 16-bit launches only, anything else takes its slab twin
+        const bool direct_ok = direct_epilogue_ok<EPI>(p) && p.splits == 1 && !p.residual && !p.x1 && !p.acc_float;
         if constexpr (EPI == EPI_F16 || EPI == EPI_BF16) {
             if (direct_ok) return launch_pp<256, 256, 1, 6, EPI, false, true>(p, st);
         }
-        tile = 14;
+        tile = tile_slab_twin(tile);
     }
     switch (tile) {
-    case 14: return launch_pp<256, 256, 1, 6, EPI>(p, st);
-    case 15: return launch_pp<128, 128, 2, 6, EPI>(p, st);
-    case 16: return launch_pp<96, 128, 2, 7, EPI>(p, st);
-    case 17: return launch_pp<192, 128, 2, 5, EPI>(p, st);
-    case 18: return launch_pp<64, 128, 2, 8, EPI>(p, st);
-    case 19: return launch_pp<128, 256, 1, 8, EPI>(p, st);
+    case TILE_PP_256x256: return launch_pp<256, 256, 1, 6, EPI>(p, st);
+    case TILE_PP_128x128: return launch_pp<128, 128, 2, 6, EPI>(p, st);
+    case TILE_PP_96x128: return launch_pp<96, 128, 2, 7, EPI>(p, st);
+    case TILE_PP_192x128: return launch_pp<192, 128, 2, 5, EPI>(p, st);
+    case TILE_PP_64x128: return launch_pp<64, 128, 2, 8, EPI>(p, st);
+    case TILE_PP_128x256: return launch_pp<128, 256, 1, 8, EPI>(p, st);
     default: break;
     }
     return fail(MQ_EINVAL, "gemm_pp: unknown tile %d", tile);

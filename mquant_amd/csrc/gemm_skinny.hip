@@ -8,9 +8,9 @@
 // work: a wave owns one 32-channel pair of the W4 image and a slice of K, pulls its 1 KiB pieces straight from HBM into
 // registers (one global_load_dwordx4 per 64-wide k-tile: the piece is already in the MFMA fragment order, no LDS), reads the
 // matching activation pieces (L2-resident, shared by every wave), unpacks the nibbles and issues V_MFMA_I32_16X16X64_I8.
-// Two kernels: gemm_skinny_wg_kernel (plan id 61, up to two row tiles) -- one workgroup per pair, its EIGHT WAVES are the K slices and
+// Two kernels: gemm_skinny_wg_kernel (TILE_SKINNY_WG, up to two row tiles) -- one workgroup per pair, its EIGHT WAVES are the K slices and
 // meet in LDS (short reductions: one launch, no workspace; long ones: a few workgroup slices on top) -- and gemm_skinny_kernel
-// (plan id 60, up to four row tiles on long reductions) -- (pairs / 4) x slices workgroups of four waves, one wave per pair and slice.
+// (TILE_SKINNY, up to four row tiles on long reductions) -- (pairs / 4) x slices workgroups of four waves, one wave per pair and slice.
 //
 // Reduction over slices of DIFFERENT workgroups: every workgroup parks its exact int32 partial sums in the split-K workspace ([slice][M][N], the
 // layout of the tiled kernels' split-K) and splitk_reduce_kernel (gemm_w4a8.hip) adds them and runs the common epilogue in a
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p)
 
 // Short reductions (K <= 4096: q|k|v, o_proj, gate|up): the K slices are the EIGHT WAVES of one workgroup, all on the same channel
 // pair; their partial sums meet in LDS and the waves share the epilogue -- no workspace, no second launch (8.2 -> ~5 us for q|k|v
-// at M = 1, profiles/r5_decode_gemm_bench.txt).  Plan id 61.
+// at M = 1, profiles/r5_decode_gemm_bench.txt).  TILE_SKINNY_WG.
 template <int EPI, int TMX>
 __global__ __launch_bounds__(512) void gemm_skinny_wg_kernel(GemmArgs p)
 {

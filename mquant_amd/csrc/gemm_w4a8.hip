@@ -37,11 +37,11 @@ int launch_gemm_pp(const GemmArgs &p, int tile, hipStream_t st);   // gemm_pp.hi
 template <int W_BITS, int EPI>
 int dispatch_ws_wgroup(const GemmArgs &p, int tile, hipStream_t st);   // gemm_ws.hip (weight-group fold in the 16x16x64 math loop)
 template <int EPI>
-int launch_gemm_skinny(const GemmArgs &p, hipStream_t st);             // gemm_skinny.hip (M <= 64 rows, W4, tiled activations; tile id 60)
+int launch_gemm_skinny(const GemmArgs &p, hipStream_t st);             // gemm_skinny.hip (M <= 64 rows, W4, tiled activations; TILE_SKINNY)
 int skinny_slices(long M, long N, long K_pad, size_t ws_bytes);
 int skinny_wg_slices(long M, long N, long K_pad, size_t ws_bytes);
 template <int EPI>
-int launch_gemm_skinny_wg(const GemmArgs &p, hipStream_t st);          // gemm_skinny.hip (M <= 16, K <= 4096: the K slices are a workgroup's waves; id 61)
+int launch_gemm_skinny_wg(const GemmArgs &p, hipStream_t st);          // gemm_skinny.hip (M <= 16, K <= 4096: the K slices are a workgroup's waves; TILE_SKINNY_WG)
 
 // GROUPED (--a_groupsize): the int32 accumulators of one activation group (64 or a multiple of 128 k) are scaled by
 // the group's activation scale of their row and added to fp32 accumulators in ascending group order; the epilogue
@@ -465,6 +465,17 @@ __global__ __launch_bounds__(512) void gemm_w4a8_pipe_kernel(GemmArgs p)
     gemm_epilogue<TM, TN, NWAVES, RING * SLOT_BYTES, 4, EPI>(p, acc, smem, wave, lane, wm, wn, m0, nt0, split);
 }
 
+// Split-K: what follows a GEMM launch that returned rc and wrote p.splits partial sums (nothing when it failed or the reduction was not split).
+template <int EPI>
+static int finish_splitk(int rc, const GemmArgs &p, hipStream_t st)
+{
+    if (rc != MQ_OK || p.splits == 1) return rc;
+    long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
+    return check_launch("splitk_reduce");
+}
+
 template <int EPI>
 static int launch_gemm_pipe(const GemmArgs &p, hipStream_t st)
 {
@@ -478,12 +489,7 @@ static int launch_gemm_pipe(const GemmArgs &p, hipStream_t st)
     set_geometry(g, 256, 256, 64, 4);
     if (!geometry_in_range(g)) return fail(MQ_EINVAL, "mq_gemm_w4a8: %u x %u x %d workgroups exceed the range of the launch-geometry arithmetic", g.m_blocks, g.n_blocks, g.splits);
     hipLaunchKernelGGL(kern, dim3(g.m_blocks * g.n_blocks * (unsigned)g.splits), dim3(512), SMEM, st, g);
-    int rc = check_launch("gemm_w4a8_pipe");
-    if (rc != MQ_OK || p.splits == 1) return rc;
-    long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-    return check_launch("splitk_reduce");
+    return finish_splitk<EPI>(check_launch("gemm_w4a8_pipe"), p, st);
 }
 
 template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int W_BITS, int EPI, int DMA_POS = 1, bool GROUPED = false>
@@ -501,12 +507,7 @@ static int launch_gemm(const GemmArgs &p, hipStream_t st)
     if (!geometry_in_range(g)) return fail(MQ_EINVAL, "mq_gemm_w4a8: %u x %u x %d workgroups exceed the range of the launch-geometry arithmetic", g.m_blocks, g.n_blocks, g.splits);
     hipLaunchKernelGGL(kern, dim3(g.m_blocks * g.n_blocks * (unsigned)g.splits),
                        dim3(WARPS_M * WARPS_N * 64), SMEM, st, g);
-    int rc = check_launch("gemm_w4a8");
-    if (rc != MQ_OK || p.splits == 1) return rc;
-    long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-    return check_launch("splitk_reduce");
+    return finish_splitk<EPI>(check_launch("gemm_w4a8"), p, st);
 }
 
 // Tile / split-K plan, from measurements on MI355X (profiles/ and DESIGN.md):
@@ -517,47 +518,52 @@ static int launch_gemm(const GemmArgs &p, hipStream_t st)
 //   * everything else is latency bound (~8 us floor per launch + ~0.3 us per k-step): 64x128
 //     tiles put two or three workgroups on every CU and measured 10-30 % faster than 128x128.
 #ifndef MQ_PLAN_WIDE_TILE
-#define MQ_PLAN_WIDE_TILE 20   // the ping-pong 256 x 256 tile with the slab-free epilogue and the next tile's stages requested ahead (round 6: -2.4 % on
-                               // gate|up, profiles/r6_pp_direct_epilogue_ab.txt; launches it does not cover take tile 14 inside launch_gemm_pp).
+#define MQ_PLAN_WIDE_TILE 20   // the ping-pong 256 x 256 tile with the slab-free epilogue and the next tile's stages requested ahead (round 6: 87.17 us
+                               // against 88.34 us for tile 14 on gate|up, profiles/r6_direct_epilogue_ab.txt; with the slab-free wave-specialised ids
+                               // +0.73 % tokens/s over the whole bench, profiles/r6_bench_ab_direct_epilogues.txt; launches it does not cover take
+                               // tile 14 inside launch_gemm_pp).
                                // A/B builds: -DMQ_PLAN_WIDE_TILE=14 (round 4/5), =13 (the software-pipelined kernel of rounds 1-3)
 #endif
 struct Plan {
-    int tile;    // index into dispatch_tile
+    int tile;    // a TileId (gemm_common.h), or whatever number mq_gemm_debug_force gave
     int splits;
 };
 
-// epi_only: 0 = any kernel; 1 = an epilogue that exists in the wave-specialised kernels only (RoPE in the store); 2 = an activation in
-// the store (GemmArgs::act): the wave-specialised tiles or the wide ping-pong tile, no split-K, no weight-streaming kernels
+enum class PlanMode {
+    ANY,      // any kernel
+    WS_ONLY,  // an epilogue that exists in the wave-specialised kernels only (RoPE in the store, group scales): no split-K
+    ACT,      // an activation in the store (GemmArgs::act): the wave-specialised tiles or the wide ping-pong tile, no split-K, no weight-streaming kernels
+};
+
+// The wave-specialised candidates of the plan, {id, rows, channels}, and the 192-row one among them (W4 only; also what the spill rule takes).
+// Round 5: the V_MFMA_I32_16X16X64_I8 twins of the round-2 tiles -- bit-identical results, 1-7 % faster per shape on one box: the 16x16x64
+// form does the same MACs with half the accumulator register traffic and the launches run at the package power limit,
+// profiles/r5_ws_tiles_ab.txt.  Round 6: the same kernels with the slab-free epilogue (gemm_ws.hip DIRECT: 0.13 ... 1.01 us less per launch,
+// profiles/r6_direct_epilogue_ab.txt); launches it does not cover (split-K, RoPE, int32 / fp32 outputs ...) fall back to the slab twin
+// inside dispatch_ws.  -DMQ_PLAN_WS_SLAB restores the round-5 ids, -DMQ_PLAN_WS_32X32 the round-2 ones.
+#ifdef MQ_PLAN_WS_32X32
+static const int WS_CAND[][3] = {{TILE_WS32_64x128, 64, 128}, {TILE_WS32_96x128, 96, 128}, {TILE_WS32_128x128, 128, 128}, {TILE_WS32_192x128, 192, 128}};
+constexpr int WS192 = TILE_WS32_192x128;
+#elif defined(MQ_PLAN_WS_SLAB)
+static const int WS_CAND[][3] = {{TILE_WS_64x128, 64, 128}, {TILE_WS_96x128_2W, 96, 128}, {TILE_WS_128x128, 128, 128}, {TILE_WS_192x128, 192, 128}};
+constexpr int WS192 = TILE_WS_192x128;
+#else
+static const int WS_CAND[][3] = {{TILE_WSD_64x128, 64, 128}, {TILE_WSD_96x128_2W, 96, 128}, {TILE_WSD_128x128, 128, 128}, {TILE_WSD_192x128, 192, 128}};
+constexpr int WS192 = TILE_WSD_192x128;
+#endif
+
 static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes, int force_tile,
-                      int force_splits, bool w4 = true, bool a_tiled = false, int epi_only = 0)
+                      int force_splits, bool w4 = true, bool a_tiled = false, PlanMode mode = PlanMode::ANY)
 {
-    const bool ws_only = epi_only == 1, act_mode = epi_only == 2;
+    const bool ws_only = mode == PlanMode::WS_ONLY, act_mode = mode == PlanMode::ACT;
     const long kps = K_pad / 128;
     const long t256 = ceil_div(M, 256) * ceil_div(N, 256);
-    Plan pl = {10, 1};
+    Plan pl = {TILE_SYM_64x128, 1};
     long best = -1, best_tiles = 0;
     if (a_tiled) {
         // wave-specialised kernels (gemm_ws.hip), every operand byte arrives as contiguous KiB pieces:
         // the bytes the busiest CU has to pull decide, ceil(tiles/256) x (BM + BN/2) per unit of K
-        // (round 5: the V_MFMA_I32_16X16X64_I8 twins of the round-2 tiles, ids 47 / 48 / 45 / 46 for 64 / 96 / 128 / 192 x 128 -- bit-identical
-        //  results, 1-7 % faster per shape on one box: the 16x16x64 form does the same MACs with half the accumulator register traffic and
-        //  the launches run at the package power limit, profiles/r5_ws_tiles_ab.txt; -DMQ_PLAN_WS_32X32 restores ids 43 / 40 / 41 / 42)
-#ifdef MQ_PLAN_WS_32X32
-        static const int cand[][3] = {{43, 64, 128}, {40, 96, 128}, {41, 128, 128}, {42, 192, 128}};
-        constexpr int WS192 = 42;
-#else
-        // round 6: ids 53 / 54 / 51 / 52 = the same kernels with the slab-free epilogue (gemm_ws.hip DIRECT: -0.6 ... -1.5 us per launch,
-        // profiles/r6_ws_direct_epilogue_ab.txt); launches it does not cover (split-K, RoPE, int32 / fp32 outputs ...) fall back to the
-        // slab twin inside dispatch_ws.  -DMQ_PLAN_WS_SLAB restores ids 47 / 48 / 45 / 46
-#ifdef MQ_PLAN_WS_SLAB
-        static const int cand[][3] = {{47, 64, 128}, {48, 96, 128}, {45, 128, 128}, {46, 192, 128}};
-        constexpr int WS192 = 46;
-#else
-        static const int cand[][3] = {{53, 64, 128}, {54, 96, 128}, {51, 128, 128}, {52, 192, 128}};
-        constexpr int WS192 = 52;
-#endif
-#endif
-        for (const auto &c : cand) {
+        for (const auto &c : WS_CAND) {
             if (c[0] == WS192 && !w4) continue;
             const long tiles = ceil_div(M, c[1]) * ceil_div(N, c[2]);
             const long cost = ceil_div(tiles, 256) * (c[1] + (w4 ? c[2] / 2 : c[2]));
@@ -566,9 +572,10 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
     } else {
         // Row-major activations: small GEMMs are bound by the row gather (~14.5 B/clk/CU out of L2,
         // tools/probes/l2_row_stride.hip); same cost model over the symmetric kernels.
-        static const int cand[][3] = {{10, 64, 128}, {31, 96, 128}, {26, 128, 128}, {35, 192, 128}, {2, 256, 128}};
+        static const int cand[][3] = {{TILE_SYM_64x128, 64, 128}, {TILE_SYM_96x128, 96, 128}, {TILE_SYM_128x128, 128, 128}, {TILE_SYM_192x128, 192, 128},
+                                      {TILE_SYM_256x128, 256, 128}};
         for (const auto &c : cand) {
-            if (c[0] == 35 && !w4) continue;
+            if (c[0] == TILE_SYM_192x128 && !w4) continue;
             const long tiles = ceil_div(M, c[1]) * ceil_div(N, c[2]);
             const long cost = ceil_div(tiles, 256) * (c[1] + (w4 ? c[2] / 2 : c[2]));   // int8 weights: one byte each
             if (best < 0 || cost < best) { best = cost; pl.tile = c[0]; }
@@ -578,17 +585,17 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
         // (an epilogue that exists in the wave-specialised kernels only -- RoPE in the store: the best of the tiles above, no split-K)
     } else if (!act_mode && a_tiled && w4 && ceil_div(N, 128) <= 65535 &&
                (M <= 16 || (M <= 32 && K_pad >= 512 && K_pad <= 4096 && N >= 2048) || (M <= 64 && kps >= 64 && ceil_div(N, 128) < 128))) {
-        // A few rows (generation steps of the exam scripts): the weight stream is the work -- gemm_skinny.hip, id 60; `splits` = its
+        // A few rows (generation steps of the exam scripts): the weight stream is the work -- gemm_skinny.hip, TILE_SKINNY; `splits` = its
         // K slices, added up by splitk_reduce_kernel.  One row tile: every decoder shape gains (48 against 80 us per layer at M = 1);
         // two to four row tiles: only the long reductions over few channel tiles do (down_proj: 23 against 36 us at M = 32) --
         // profiles/r5_decode_gemm_bench.txt
-        pl.tile = 60;
+        pl.tile = TILE_SKINNY;
         pl.splits = have_ws ? skinny_slices(M, N, K_pad, ws_bytes) : 1;
         if (M <= 32 && K_pad >= 512 && K_pad <= 4096 && N >= 2048) {   // short reduction, enough pairs: the slices are the eight waves of a workgroup
-            pl.tile = 61;
+            pl.tile = TILE_SKINNY_WG;
             pl.splits = 1;
         } else if (M <= 32 && K_pad > 4096 && have_ws) {               // long reduction: a few workgroup slices of eight waves each
-            pl.tile = 61;
+            pl.tile = TILE_SKINNY_WG;
             pl.splits = skinny_wg_slices(M, N, K_pad, ws_bytes);
         }
     } else if (act_mode && !(w4 && a_tiled)) {
@@ -597,7 +604,7 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
         // gate|up: with tiled activations the 8-wave ping-pong kernel (gemm_pp.hip, round 4: 93-101 us against 108-116
         // for the software-pipelined tile 13 and 110-112 for the 16-wave tile 3, profiles/r4_pp_ab.txt); with row-major
         // activations the 16-wave kernel
-        pl.tile = (w4 && a_tiled) ? MQ_PLAN_WIDE_TILE : 3;
+        pl.tile = (w4 && a_tiled) ? MQ_PLAN_WIDE_TILE : TILE_SYM_256x256;
         // ... unless a handful of 256 x 256 tiles spill into one more round (Qwen-VL w1|w2: 258 tiles; InternVL2 wqkv at
         // batch 4: 288): a round of the 256^2 kernel is ~57 us whether 2 or 256 tiles run in it.  Then the 192 x 128
         // wave-specialised tile is compared on measured per-tile times (us: f0 + c per 128-deep k-step; a partial last
@@ -607,13 +614,7 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
             auto rounds = [](long tiles) { const long f = tiles / 256, r = tiles % 256; return (float)f + (r ? 0.8f + 0.2f * (float)r / 256.0f : 0.0f); };
             const float t_pipe = rounds(t256) * (4.0f + 1.65f * (float)kps);
             const float t_192 = rounds(ceil_div(M, 192) * ceil_div(N, 128)) * (7.8f + 0.55f * (float)kps);
-#ifdef MQ_PLAN_WS_32X32
-            if (t_192 < t_pipe) pl.tile = 42;
-#elif defined(MQ_PLAN_WS_SLAB)
-            if (t_192 < t_pipe) pl.tile = 46;
-#else
-            if (t_192 < t_pipe) pl.tile = 52;
-#endif
+            if (t_192 < t_pipe) pl.tile = WS192;
         }
     } else if (a_tiled && best >= 0 && ceil_div(M, 96) * ceil_div(N, 128) >= 128) {
         // enough 96..192 x 128 tiles for most CUs: the wave-specialised kernel walks the whole reduction
@@ -630,11 +631,10 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
         long s = (252 + t256 - 1) / t256;
         if (s > 8) s = 8;
         while (s > 1 && ((size_t)(s * M * N * 4) > ws_bytes || kps / s < 8)) --s;
-        if (s > 1) { pl.tile = 3; pl.splits = (int)s; }
+        if (s > 1) { pl.tile = TILE_SYM_256x256; pl.splits = (int)s; }
     }
-    if (force_tile >= 0 && (!ws_only || (force_tile >= 40 && force_tile < 60))
-        && (!act_mode || (force_tile >= 40 && force_tile < 60) || force_tile == 14 || force_tile == 19 || force_tile == 20)) {
-        if ((pl.tile == 60 || pl.tile == 61) && force_tile != pl.tile) pl.splits = 1;   // (the slices were the skinny kernel's)
+    if (force_tile >= 0 && (!ws_only || tile_is_ws(force_tile)) && (!act_mode || tile_has_act(force_tile))) {
+        if (tile_is_skinny(pl.tile) && force_tile != pl.tile) pl.splits = 1;   // (the slices were the skinny kernel's)
         pl.tile = force_tile;
     }
     if (force_splits > 0 && !ws_only && !act_mode) pl.splits = force_splits;
@@ -648,63 +648,38 @@ static Plan make_plan(long M, long N, long K_pad, bool have_ws, size_t ws_bytes,
 template <int W_BITS, int EPI>
 static int dispatch_tile(const GemmArgs &p, int tile, hipStream_t st)
 {
-    if (tile >= 40 && tile < 60) {
+    if (tile_is_ws(tile)) {
         if (!p.a_tiled) return fail(MQ_EINVAL, "mq_gemm_w4a8: tile %d needs activations in the tiled layout (lda = MQ_LD_TILED)", tile);
-        const int rc = dispatch_ws<W_BITS, EPI>(p, tile, st);
-        if (rc != MQ_OK || p.splits == 1) return rc;
-        long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-        return check_launch("splitk_reduce");
+        return finish_splitk<EPI>(dispatch_ws<W_BITS, EPI>(p, tile, st), p, st);
     }
     switch (tile) {
-    case 1:
+    case TILE_SYM_256x256_8W:
         if constexpr (W_BITS == 4) return launch_gemm<256, 256, 2, 4, 3, W_BITS, EPI>(p, st);
         else return launch_gemm<256, 128, 4, 2, 3, W_BITS, EPI>(p, st);  // int8 weights: 3 x 64 KiB would not fit
-    case 2: return launch_gemm<256, 128, 4, 2, 3, W_BITS, EPI>(p, st);
-    case 3:
+    case TILE_SYM_256x128: return launch_gemm<256, 128, 4, 2, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_256x256:
         if constexpr (W_BITS == 4) return launch_gemm<256, 256, 4, 4, 3, W_BITS, EPI>(p, st);
         else return launch_gemm<256, 128, 4, 2, 3, W_BITS, EPI>(p, st);
-    case 4: return launch_gemm<128, 256, 2, 4, 3, W_BITS, EPI>(p, st);
-    case 5: return launch_gemm<256, 128, 2, 4, 3, W_BITS, EPI>(p, st);
-    case 13: if constexpr (W_BITS == 4) return launch_gemm_pipe<EPI>(p, st); else break;
-    case 14: case 15: case 16: case 17: case 18: case 19: case 20:
+    case TILE_SYM_128x256: return launch_gemm<128, 256, 2, 4, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_256x128_2x4: return launch_gemm<256, 128, 2, 4, 3, W_BITS, EPI>(p, st);
+    case TILE_PIPE_256x256: if constexpr (W_BITS == 4) return launch_gemm_pipe<EPI>(p, st); else break;
+    case TILE_PP_256x256: case TILE_PP_128x128: case TILE_PP_96x128: case TILE_PP_192x128: case TILE_PP_64x128: case TILE_PP_128x256:
+    case TILE_PP_256x256_DIRECT:
         if constexpr (W_BITS == 4) {
             if (!p.a_tiled) return fail(MQ_EINVAL, "mq_gemm_w4a8: tile %d needs activations in the tiled layout (lda = MQ_LD_TILED)", tile);
-            const int rc = launch_gemm_pp<EPI>(p, tile, st);
-            if (rc != MQ_OK || p.splits == 1) return rc;
-            long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            return check_launch("splitk_reduce");
+            return finish_splitk<EPI>(launch_gemm_pp<EPI>(p, tile, st), p, st);
         } else break;
-    case 60:
-        if constexpr (W_BITS == 4) {
-            const int rc = launch_gemm_skinny<EPI>(p, st);
-            if (rc != MQ_OK || p.splits == 1) return rc;
-            long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            return check_launch("splitk_reduce");
-        } else break;
-    case 61:
-        if constexpr (W_BITS == 4) {
-            const int rc = launch_gemm_skinny_wg<EPI>(p, st);
-            if (rc != MQ_OK || p.splits == 1) return rc;
-            long blocks = ceil_div(p.M * ceil_div(p.N, 4), 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            return check_launch("splitk_reduce");
-        } else break;
-    case 10: return launch_gemm<64, 128, 2, 2, 3, W_BITS, EPI>(p, st);
-    case 11: return launch_gemm<128, 64, 2, 2, 3, W_BITS, EPI>(p, st);
-    case 12: return launch_gemm<128, 128, 4, 2, 3, W_BITS, EPI>(p, st);
-    case 26: return launch_gemm<128, 128, 2, 4, 3, W_BITS, EPI>(p, st);
-    case 31: return launch_gemm<96, 128, 1, 4, 3, W_BITS, EPI>(p, st);
-    case 35: if constexpr (W_BITS == 4) return launch_gemm<192, 128, 2, 4, 3, W_BITS, EPI>(p, st); else break;
+    case TILE_SKINNY: if constexpr (W_BITS == 4) return finish_splitk<EPI>(launch_gemm_skinny<EPI>(p, st), p, st); else break;
+    case TILE_SKINNY_WG: if constexpr (W_BITS == 4) return finish_splitk<EPI>(launch_gemm_skinny_wg<EPI>(p, st), p, st); else break;
+    case TILE_SYM_64x128: return launch_gemm<64, 128, 2, 2, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_128x64: return launch_gemm<128, 64, 2, 2, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_128x128_4x2: return launch_gemm<128, 128, 4, 2, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_128x128: return launch_gemm<128, 128, 2, 4, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_96x128: return launch_gemm<96, 128, 1, 4, 3, W_BITS, EPI>(p, st);
+    case TILE_SYM_192x128: if constexpr (W_BITS == 4) return launch_gemm<192, 128, 2, 4, 3, W_BITS, EPI>(p, st); else break;
     default: break;
     }
-    return launch_gemm<128, 128, 2, 2, 3, W_BITS, EPI>(p, st);
+    return launch_gemm<128, 128, 2, 2, 3, W_BITS, EPI>(p, st);   // any other id, and the int4-only ids with int8 weights
 }
 
 // test / tuning overrides of the plan (mq_gemm_debug_force): thread-local, so they change the dispatch of the
@@ -712,142 +687,164 @@ static int dispatch_tile(const GemmArgs &p, int tile, hipStream_t st)
 static thread_local int g_force_tile = -1, g_force_splits = 0;
 thread_local int g_gemm_force_xm = 0;
 
-static int gemm_common(const int8_t *a, long lda, const void *w, int w_bits, long M, long N,
-                       long K_pad, float s_x0, float s_x1, const uint8_t *row_sel,
-                       const float *s_w, const float *bias, const float *x0, const float *w0,
-                       void *out, int epi, long ldo, void *workspace, size_t workspace_bytes,
-                       void *stream, const float *sx_vec = nullptr, const void *residual = nullptr,
-                       long ldr = 0, const float *sx_groups = nullptr, long n_groups = 0, int group_k = 0,
-                       const float *x1 = nullptr, const float *w1 = nullptr, const float *shift_groups = nullptr,
-                       const float *wsum_groups = nullptr, const float *sw_groups = nullptr,
-                       const void *rope_cos = nullptr, const void *rope_sin = nullptr, long rope_cols = 0, int act = MQ_ACT_NONE)
+// One call of the dispatcher: what an entry point was given, by name.  A member an entry point does not set keeps the value that turns its
+// epilogue term off.
+struct GemmCall {
+    const int8_t *a = nullptr;
+    long lda = 0;
+    const void *w = nullptr;
+    int w_bits = 0;
+    long M = 0, N = 0, K_pad = 0;
+    float s_x0 = 1.0f, s_x1 = 1.0f;   // (1.0 where the row scale is elsewhere: x 1.0 in the epilogue is exact)
+    const uint8_t *row_sel = nullptr;
+    const float *s_w = nullptr, *bias = nullptr, *x0 = nullptr, *w0 = nullptr, *x1 = nullptr, *w1 = nullptr, *sx_vec = nullptr;
+    const float *sx_groups = nullptr, *shift_groups = nullptr, *wsum_groups = nullptr, *sw_groups = nullptr;
+    long n_groups = 0;
+    int group_k = 0;
+    const void *residual = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
+    long ldr = 0, rope_cols = 0;
+    int act = MQ_ACT_NONE;
+    void *out = nullptr;
+    int epi = EPI_F32;
+    long ldo = 0;
+    void *workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void *stream = nullptr;
+};
+
+// The eleven arguments every entry point has, in the order its signature has them.
+static GemmCall gemm_call(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad, void *out, int epi, long ldo, void *stream)
 {
+    GemmCall c;
+    c.a = a; c.lda = lda; c.w = w; c.w_bits = w_bits; c.M = M; c.N = N; c.K_pad = K_pad; c.out = out; c.epi = epi; c.ldo = ldo; c.stream = stream;
+    return c;
+}
+
+// Runtime (w_bits, epi) -> template arguments: f(integral_constant<int, W_BITS>, integral_constant<int, EPI>).  WITH_I32 = false is for the
+// callers that have no int32 form (group scales: whatever is not a 16-bit type takes the fp32 one, the caller has refused everything else).
+template <bool WITH_I32, class F>
+static int with_bits_epi(int w_bits, int epi, F f)
+{
+    auto on_epi = [&](auto wb) {
+        if (epi == EPI_F16) return f(wb, std::integral_constant<int, EPI_F16>{});
+        if (epi == EPI_BF16) return f(wb, std::integral_constant<int, EPI_BF16>{});
+        if (!WITH_I32 || epi == EPI_F32) return f(wb, std::integral_constant<int, EPI_F32>{});
+        if constexpr (WITH_I32) {
+            if (epi == EPI_I32) return f(wb, std::integral_constant<int, EPI_I32>{});
+        }
+        return fail(MQ_EINVAL, "mq_gemm_w4a8: unknown output dtype %d", epi);
+    };
+    return w_bits == 4 ? on_epi(std::integral_constant<int, 4>{}) : on_epi(std::integral_constant<int, 8>{});
+}
+
+static int gemm_common(const GemmCall &c)
+{
+    const long M = c.M, N = c.N, K_pad = c.K_pad;
     MQ_REQUIRE(M >= 0 && N >= 0 && K_pad >= 0, "mq_gemm_w4a8: negative shape");
     if (M == 0 || N == 0) return MQ_OK;
-    MQ_REQUIRE(a && w && out, "mq_gemm_w4a8: null buffer");
+    MQ_REQUIRE(c.a && c.w && c.out, "mq_gemm_w4a8: null buffer");
     MQ_REQUIRE(K_pad > 0 && K_pad % 128 == 0, "mq_gemm_w4a8: K_pad=%ld must be a positive multiple of 128", K_pad);
-    const bool a_tiled = (lda == MQ_LD_TILED);
-    MQ_REQUIRE(((uintptr_t)a) % 16 == 0 && (a_tiled || (lda >= K_pad && lda % 16 == 0)),
+    const bool a_tiled = (c.lda == MQ_LD_TILED);
+    MQ_REQUIRE(((uintptr_t)c.a) % 16 == 0 && (a_tiled || (c.lda >= K_pad && c.lda % 16 == 0)),
                "mq_gemm_w4a8: activations must be 16-byte aligned with lda %% 16 == 0 and lda >= K_pad (or lda = MQ_LD_TILED)");
-    MQ_REQUIRE(((uintptr_t)w) % 16 == 0, "mq_gemm_w4a8: weight image must be 16-byte aligned");
-    MQ_REQUIRE(w_bits == 4 || w_bits == 8, "mq_gemm_w4a8: w_bits must be 4 or 8");
-    MQ_REQUIRE(ldo >= (act == MQ_ACT_SILU_MUL ? N / 2 : N), "mq_gemm_w4a8: ldo < N");
-    MQ_REQUIRE(epi == EPI_I32 || s_w || sw_groups, "mq_gemm_w4a8: s_w is required");
-    MQ_REQUIRE((x0 == nullptr) == (w0 == nullptr), "mq_gemm_w4a8: x0 and w0 go together");
-    MQ_REQUIRE((x1 == nullptr) == (w1 == nullptr) && (x1 == nullptr || epi != EPI_I32), "mq_gemm_w4a8: x1 and w1 go together (floating-point outputs)");
+    MQ_REQUIRE(((uintptr_t)c.w) % 16 == 0, "mq_gemm_w4a8: weight image must be 16-byte aligned");
+    MQ_REQUIRE(c.w_bits == 4 || c.w_bits == 8, "mq_gemm_w4a8: w_bits must be 4 or 8");
+    MQ_REQUIRE(c.ldo >= (c.act == MQ_ACT_SILU_MUL ? N / 2 : N), "mq_gemm_w4a8: ldo < N");
+    MQ_REQUIRE(c.epi == EPI_I32 || c.s_w || c.sw_groups, "mq_gemm_w4a8: s_w is required");
+    MQ_REQUIRE((c.x0 == nullptr) == (c.w0 == nullptr), "mq_gemm_w4a8: x0 and w0 go together");
+    MQ_REQUIRE((c.x1 == nullptr) == (c.w1 == nullptr) && (c.x1 == nullptr || c.epi != EPI_I32), "mq_gemm_w4a8: x1 and w1 go together (floating-point outputs)");
     // int32 headroom: |acc| <= K * 128 * 8 * 16 (int4 in the high nibble) or K * 128 * 128
     MQ_REQUIRE(K_pad <= 131072L, "mq_gemm_w4a8: K too large for int32 accumulation");
-    MQ_REQUIRE(!workspace || ((uintptr_t)workspace) % 16 == 0, "mq_gemm_w4a8: workspace must be 16-byte aligned");
+    MQ_REQUIRE(!c.workspace || ((uintptr_t)c.workspace) % 16 == 0, "mq_gemm_w4a8: workspace must be 16-byte aligned");
     GemmArgs p;
-    p.a = a; p.lda = lda; p.a_tiled = a_tiled; p.w = (const uint8_t *)w; p.M = M; p.N = N; p.K_pad = K_pad;
+    p.a = c.a; p.lda = c.lda; p.a_tiled = a_tiled; p.w = (const uint8_t *)c.w; p.M = M; p.N = N; p.K_pad = K_pad;
     p.n_tiles = ceil_div(N, 16);
     p.n_pairs = ceil_div(N, 32);
-    p.sx0 = s_x0; p.sx1 = s_x1; p.row_sel = row_sel; p.s_w = s_w; p.bias = bias; p.x0 = x0; p.w0 = w0;
-    p.sx_vec = sx_vec;
-    p.x1 = x1; p.w1 = w1;
-    p.residual = residual; p.ldr = ldr;
-    MQ_REQUIRE(!residual || (epi != EPI_I32 && ldr >= N), "mq_gemm_w4a8: bad residual geometry");
-    p.res_vec = residual && (((uintptr_t)residual) % 16 == 0) && ((ldr * ((epi == EPI_F32) ? 4 : 2)) % 16 == 0);
-    p.out = out; p.ldo = ldo;
-    if (sx_groups || sw_groups) {
+    p.sx0 = c.s_x0; p.sx1 = c.s_x1; p.row_sel = c.row_sel; p.s_w = c.s_w; p.bias = c.bias; p.x0 = c.x0; p.w0 = c.w0;
+    p.sx_vec = c.sx_vec;
+    p.x1 = c.x1; p.w1 = c.w1;
+    p.residual = c.residual; p.ldr = c.ldr;
+    MQ_REQUIRE(!c.residual || (c.epi != EPI_I32 && c.ldr >= N), "mq_gemm_w4a8: bad residual geometry");
+    p.res_vec = c.residual && (((uintptr_t)c.residual) % 16 == 0) && ((c.ldr * ((c.epi == EPI_F32) ? 4 : 2)) % 16 == 0);
+    p.out = c.out; p.ldo = c.ldo;
+    p.vec_ok = (N % 8 == 0) && (c.ldo % 8 == 0) && (((uintptr_t)c.out) % 16 == 0);
+    auto al16 = [](const void *q) { return q == nullptr || ((uintptr_t)q) % 16 == 0; };
+    hipStream_t st = (hipStream_t)c.stream;
+    if (c.sx_groups || c.sw_groups) {
         // group-wise activation and / or weight scales: the symmetric 128 x 128 kernel, no split-K, floating-point outputs only
-        MQ_REQUIRE(epi != EPI_I32 && group_k > 0 && (group_k == 64 || group_k % 128 == 0) && K_pad % 64 == 0 && !x1 && (!sx_vec || (sw_groups && !sx_groups)),
-                   "mq_gemm_w4a8_groupscale: group size %d (64 or a multiple of 128)", group_k);
-        MQ_REQUIRE((shift_groups == nullptr) == (wsum_groups == nullptr), "mq_gemm_w4a8_groupscale: shift_groups and wsum_groups go together");
-        MQ_REQUIRE(!(sw_groups && shift_groups), "mq_gemm_w4a8_wgroupscale: asymmetric activation groups are not combined with weight groups");
-        p.sx_groups = sx_groups; p.sw_groups = sw_groups; p.n_groups = n_groups; p.group_k = group_k; p.acc_float = 1;
-        p.shift_groups = shift_groups; p.wsum_groups = wsum_groups;
+        MQ_REQUIRE(c.epi != EPI_I32 && c.group_k > 0 && (c.group_k == 64 || c.group_k % 128 == 0) && K_pad % 64 == 0 && !c.x1
+                       && (!c.sx_vec || (c.sw_groups && !c.sx_groups)),
+                   "mq_gemm_w4a8_groupscale: group size %d (64 or a multiple of 128)", c.group_k);
+        MQ_REQUIRE((c.shift_groups == nullptr) == (c.wsum_groups == nullptr), "mq_gemm_w4a8_groupscale: shift_groups and wsum_groups go together");
+        MQ_REQUIRE(!(c.sw_groups && c.shift_groups), "mq_gemm_w4a8_wgroupscale: asymmetric activation groups are not combined with weight groups");
+        p.sx_groups = c.sx_groups; p.sw_groups = c.sw_groups; p.n_groups = c.n_groups; p.group_k = c.group_k; p.acc_float = 1;
+        p.shift_groups = c.shift_groups; p.wsum_groups = c.wsum_groups;
         p.splits = 1; p.partial = nullptr;
-        p.vec_ok = (N % 8 == 0) && (ldo % 8 == 0) && (((uintptr_t)out) % 16 == 0);
-        auto al = [](const void *q) { return q == nullptr || ((uintptr_t)q) % 16 == 0; };
-        p.par_ok = al(s_w) && al(bias) && al(w0);
-        hipStream_t gst = (hipStream_t)stream;
-        if (a_tiled && !shift_groups && (!sw_groups || (N % 4 == 0 && ((uintptr_t)sw_groups) % 16 == 0)) && g_force_tile != 26) {
+        p.par_ok = al16(c.s_w) && al16(c.bias) && al16(c.w0);
+        if (a_tiled && !c.shift_groups && (!c.sw_groups || (N % 4 == 0 && ((uintptr_t)c.sw_groups) % 16 == 0)) && g_force_tile != TILE_SYM_128x128) {
             // symmetric group scales (weights, activations or both) on tiled activations, groups of 64 or of whole k-steps: the fold rides in the
-            // wave-specialised 16x16x64 kernels (5.5-9 x faster than the round-1 kernel below, profiles/r5_wgroup_gemm_*.txt);
+            // wave-specialised 16x16x64 kernels (weight groups of 128: 1.8-2.4 x the per-channel GEMM of the shape, profiles/r5_group_gemm_ws_fold.txt,
+            // against 5.8-8.8 x on the round-1 kernel below, profiles/r5_group_gemm_round1_kernel.txt);
             // mq_gemm_debug_force(26) keeps the round-1 kernel for A/B
-            const Plan gpl = make_plan(M, N, K_pad, false, 0, g_force_tile, 0, w_bits == 4, true, true);
-            if (w_bits == 4) {
-                switch (epi) {
-                case EPI_F16: return dispatch_ws_wgroup<4, EPI_F16>(p, gpl.tile, gst);
-                case EPI_BF16: return dispatch_ws_wgroup<4, EPI_BF16>(p, gpl.tile, gst);
-                default: return dispatch_ws_wgroup<4, EPI_F32>(p, gpl.tile, gst);
-                }
-            }
-            switch (epi) {
-            case EPI_F16: return dispatch_ws_wgroup<8, EPI_F16>(p, gpl.tile, gst);
-            case EPI_BF16: return dispatch_ws_wgroup<8, EPI_BF16>(p, gpl.tile, gst);
-            default: return dispatch_ws_wgroup<8, EPI_F32>(p, gpl.tile, gst);
-            }
+            const Plan gpl = make_plan(M, N, K_pad, false, 0, g_force_tile, 0, c.w_bits == 4, true, PlanMode::WS_ONLY);
+            return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) {
+                return dispatch_ws_wgroup<decltype(wb)::value, decltype(e)::value>(p, gpl.tile, st);
+            });
         }
-        if (w_bits == 4) {
-            switch (epi) {
-            case EPI_F16: return launch_gemm<128, 128, 2, 4, 3, 4, EPI_F16, 1, true>(p, gst);
-            case EPI_BF16: return launch_gemm<128, 128, 2, 4, 3, 4, EPI_BF16, 1, true>(p, gst);
-            default: return launch_gemm<128, 128, 2, 4, 3, 4, EPI_F32, 1, true>(p, gst);
-            }
-        }
-        switch (epi) {
-        case EPI_F16: return launch_gemm<128, 128, 2, 4, 3, 8, EPI_F16, 1, true>(p, gst);
-        case EPI_BF16: return launch_gemm<128, 128, 2, 4, 3, 8, EPI_BF16, 1, true>(p, gst);
-        default: return launch_gemm<128, 128, 2, 4, 3, 8, EPI_F32, 1, true>(p, gst);
-        }
+        return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) {
+            return launch_gemm<128, 128, 2, 4, 3, decltype(wb)::value, decltype(e)::value, 1, true>(p, st);
+        });
     }
-    if (act != MQ_ACT_NONE) {
+    if (c.act != MQ_ACT_NONE) {
         // the activation lives in the act paths of the wave-specialised / ping-pong epilogues: everything they rely on is checked HERE
-        MQ_REQUIRE(act == MQ_ACT_SILU_MUL || act == MQ_ACT_QUICK_GELU, "mq_gemm_w4a8_act_ws: unknown activation %d", act);
-        MQ_REQUIRE(a_tiled && epi != EPI_I32 && !residual && !x0 && !x1 && !sx_groups && !sw_groups && !rope_cos,
+        MQ_REQUIRE(c.act == MQ_ACT_SILU_MUL || c.act == MQ_ACT_QUICK_GELU, "mq_gemm_w4a8_act_ws: unknown activation %d", c.act);
+        MQ_REQUIRE(a_tiled && c.epi != EPI_I32 && !c.residual && !c.x0 && !c.x1 && !c.sx_groups && !c.sw_groups && !c.rope_cos,
                    "mq_gemm_w4a8_act_ws: needs tiled activations (lda = MQ_LD_TILED), a floating-point output and no residual / rank-1 / group / RoPE terms");
-        const long n_out = act == MQ_ACT_SILU_MUL ? N / 2 : N;
-        MQ_REQUIRE(act != MQ_ACT_SILU_MUL || N % 64 == 0, "mq_gemm_w4a8_act_ws: silu(gate)*up needs N = 2 x (a multiple of 32) channels, gate then up (N = %ld)", N);
-        MQ_REQUIRE(n_out % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out) % 16 == 0, "mq_gemm_w4a8_act_ws: output columns and ldo must be multiples of 8, out 16-byte aligned");
+        const long n_out = c.act == MQ_ACT_SILU_MUL ? N / 2 : N;
+        MQ_REQUIRE(c.act != MQ_ACT_SILU_MUL || N % 64 == 0, "mq_gemm_w4a8_act_ws: silu(gate)*up needs N = 2 x (a multiple of 32) channels, gate then up (N = %ld)", N);
+        MQ_REQUIRE(n_out % 8 == 0 && c.ldo % 8 == 0 && ((uintptr_t)c.out) % 16 == 0, "mq_gemm_w4a8_act_ws: output columns and ldo must be multiples of 8, out 16-byte aligned");
         // (every form of the activation epilogue reads s_w and bias 16 bytes at a time, gemm_common.h: a view at a 4-byte offset -- a slice
         //  of a fused parameter tensor -- is refused here rather than handed to unaligned 16-byte loads)
-        MQ_REQUIRE(((uintptr_t)s_w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0, "mq_gemm_w4a8_act_ws: s_w and bias must be 16-byte aligned");
-        p.act = act;
+        MQ_REQUIRE(((uintptr_t)c.s_w) % 16 == 0 && ((uintptr_t)c.bias) % 16 == 0, "mq_gemm_w4a8_act_ws: s_w and bias must be 16-byte aligned");
+        p.act = c.act;
     }
-    const bool rope = rope_cos != nullptr;
+    const bool rope = c.rope_cos != nullptr;
     if (rope) {
         // RoPE in the store lives in the fast path of the wave-specialised epilogue: everything that path needs is checked HERE
         // (a launch that fell back to the general loop would silently skip the rotation)
-        MQ_REQUIRE(rope_sin && a_tiled && (epi == EPI_F16 || epi == EPI_BF16) && !residual && rope_cols > 0 && rope_cols % 128 == 0 && rope_cols <= N
-                       && N % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)rope_cos) % 16 == 0 && ((uintptr_t)rope_sin) % 16 == 0,
+        MQ_REQUIRE(c.rope_sin && a_tiled && (c.epi == EPI_F16 || c.epi == EPI_BF16) && !c.residual && c.rope_cols > 0 && c.rope_cols % 128 == 0 && c.rope_cols <= N
+                       && N % 8 == 0 && c.ldo % 8 == 0 && ((uintptr_t)c.out) % 16 == 0 && ((uintptr_t)c.rope_cos) % 16 == 0 && ((uintptr_t)c.rope_sin) % 16 == 0,
                    "mq_gemm_w4a8_rope_ws: needs tiled activations, a 16-bit 16-byte aligned output with N and ldo multiples of 8, heads of 128 (rope_cols a multiple of 128, at most N) and 16-byte aligned tables");
-        p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_cols = rope_cols;
+        p.rope_cos = c.rope_cos; p.rope_sin = c.rope_sin; p.rope_cols = c.rope_cols;
     }
-    Plan pl = make_plan(M, N, K_pad, workspace != nullptr && !rope && act == MQ_ACT_NONE, workspace_bytes, g_force_tile,
-                        workspace ? g_force_splits : 0, w_bits == 4, a_tiled, rope ? 1 : (act != MQ_ACT_NONE ? 2 : 0));
-    if (act != MQ_ACT_NONE && !(pl.tile >= 40 && pl.tile < 60) && pl.tile != 14 && pl.tile != 19 && pl.tile != 20) {
+    const bool act = c.act != MQ_ACT_NONE;
+    Plan pl = make_plan(M, N, K_pad, c.workspace != nullptr && !rope && !act, c.workspace_bytes, g_force_tile,
+                        c.workspace ? g_force_splits : 0, c.w_bits == 4, a_tiled, rope ? PlanMode::WS_ONLY : (act ? PlanMode::ACT : PlanMode::ANY));
+    if (act && !tile_has_act(pl.tile)) {
         // the activation epilogue exists in the 256-wide ping-pong tiles (a wave holds a gate pair AND its up pair) and in the
         // wave-specialised kernels: anything else the plan came up with takes the best wave-specialised tile
-        pl.tile = make_plan(M, N, K_pad, false, 0, -1, 0, w_bits == 4, a_tiled, 1).tile;
+        pl.tile = make_plan(M, N, K_pad, false, 0, -1, 0, c.w_bits == 4, a_tiled, PlanMode::WS_ONLY).tile;
     }
     p.splits = pl.splits;
-    p.partial = (int32_t *)workspace;
-    auto al16 = [](const void *q) { return q == nullptr || ((uintptr_t)q) % 16 == 0; };
-    const size_t osz = (epi == EPI_F16 || epi == EPI_BF16) ? 2 : 4;
-    p.vec_ok = (N % 8 == 0) && (ldo % 8 == 0) && (((uintptr_t)out) % 16 == 0);
-    p.par_ok = al16(s_w) && al16(bias) && al16(w0) && al16(w1);
-    (void)osz;
+    p.partial = (int32_t *)c.workspace;
+    p.par_ok = al16(c.s_w) && al16(c.bias) && al16(c.w0) && al16(c.w1);
     if (p.splits > 1)
-        MQ_REQUIRE((size_t)p.splits * M * N * 4 <= workspace_bytes, "mq_gemm_w4a8: workspace too small for split-K");
-    hipStream_t st = (hipStream_t)stream;
-    if (w_bits == 4) {
-        switch (epi) {
-        case EPI_F16: return dispatch_tile<4, EPI_F16>(p, pl.tile, st);
-        case EPI_BF16: return dispatch_tile<4, EPI_BF16>(p, pl.tile, st);
-        case EPI_F32: return dispatch_tile<4, EPI_F32>(p, pl.tile, st);
-        case EPI_I32: return dispatch_tile<4, EPI_I32>(p, pl.tile, st);
-        }
-    } else {
-        switch (epi) {
-        case EPI_F16: return dispatch_tile<8, EPI_F16>(p, pl.tile, st);
-        case EPI_BF16: return dispatch_tile<8, EPI_BF16>(p, pl.tile, st);
-        case EPI_F32: return dispatch_tile<8, EPI_F32>(p, pl.tile, st);
-        case EPI_I32: return dispatch_tile<8, EPI_I32>(p, pl.tile, st);
-        }
-    }
-    return fail(MQ_EINVAL, "mq_gemm_w4a8: unknown output dtype %d", epi);
+        MQ_REQUIRE((size_t)p.splits * M * N * 4 <= c.workspace_bytes, "mq_gemm_w4a8: workspace too small for split-K");
+    return with_bits_epi<true>(c.w_bits, c.epi, [&](auto wb, auto e) { return dispatch_tile<decltype(wb)::value, decltype(e)::value>(p, pl.tile, st); });
+}
+
+// The checks the entry points share.  fn: the entry point's own name, so that a refusal begins with the function the caller called.
+static int check_float_dtype(const char *fn, int out_dtype)
+{
+    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32) return fail(MQ_EINVAL, "%s: unknown output dtype %d", fn, out_dtype);
+    return MQ_OK;
+}
+
+static int check_groups_cover(const char *fn, long n_groups, int group_k, long K_pad)
+{
+    if ((long)group_k * n_groups > K_pad || (long)group_k * n_groups + 127 < K_pad)
+        return fail(MQ_EINVAL, "%s: %ld groups of %d do not cover K_pad=%ld", fn, n_groups, group_k, K_pad);
+    return MQ_OK;
 }
 
 }  // namespace mq
@@ -867,10 +864,10 @@ extern "C" int mq_gemm_w4a8(const int8_t *a, long lda, const void *w, int w_bits
                             const float *s_w, const float *bias, const float *x0, const float *w0,
                             void *out, int out_dtype, long ldo, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8: unknown output dtype %d", out_dtype);
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x0, s_x1, row_sel, s_w, bias, x0, w0,
-                           out, out_dtype, ldo, nullptr, 0, stream);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x0; c.s_x1 = s_x1; c.row_sel = row_sel; c.s_w = s_w; c.bias = bias; c.x0 = x0; c.w0 = w0;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N,
@@ -879,10 +876,11 @@ extern "C" int mq_gemm_w4a8_ws(const int8_t *a, long lda, const void *w, int w_b
                                const float *w0, void *out, int out_dtype, long ldo,
                                void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_ws: unknown output dtype %d", out_dtype);
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x0, s_x1, row_sel, s_w, bias, x0, w0,
-                           out, out_dtype, ldo, workspace, workspace_bytes, stream);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x0; c.s_x1 = s_x1; c.row_sel = row_sel; c.s_w = s_w; c.bias = bias; c.x0 = x0; c.w0 = w0;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_residual_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N,
@@ -891,12 +889,13 @@ extern "C" int mq_gemm_w4a8_residual_ws(const int8_t *a, long lda, const void *w
                                         const void *residual, long ldr, void *out, int out_dtype, long ldo,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_residual_ws: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!residual) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_residual_ws: residual is required");
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x0, s_x1, row_sel, s_w, bias, x0, w0,
-                           out, out_dtype, ldo, workspace, workspace_bytes, stream, nullptr, residual, ldr);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x0; c.s_x1 = s_x1; c.row_sel = row_sel; c.s_w = s_w; c.bias = bias; c.x0 = x0; c.w0 = w0; c.residual = residual; c.ldr = ldr;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_rope_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad, float s_x0, float s_x1,
@@ -908,22 +907,23 @@ extern "C" int mq_gemm_w4a8_rope_ws(const int8_t *a, long lda, const void *w, in
     if (head_dim != 128) return mq::fail(MQ_EUNSUPPORTED, "mq_gemm_w4a8_rope_ws: head_dim %d (the fused form needs 128 = one output tile; use mq_rope_inplace)", head_dim);
     if (M == 0 || N == 0) return MQ_OK;
     if (!rope_cos || !rope_sin) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_rope_ws: the cos / sin tables are required");
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x0, s_x1, row_sel, s_w, bias, nullptr, nullptr, out, out_dtype, ldo,
-                           nullptr, 0, stream, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           rope_cos, rope_sin, rope_cols);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x0; c.s_x1 = s_x1; c.row_sel = row_sel; c.s_w = s_w; c.bias = bias;
+    c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_cols = rope_cols;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_act_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad, float s_x0, float s_x1,
                                    const uint8_t *row_sel, const float *s_x_rows, const float *s_w, const float *bias, int act,
                                    void *out, int out_dtype, long ldo, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_act_ws: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (lda != MQ_LD_TILED) return mq::fail(MQ_EUNSUPPORTED, "mq_gemm_w4a8_act_ws: needs activations in the tiled layout (lda = MQ_LD_TILED)");
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x_rows ? 1.0f : s_x0, s_x_rows ? 1.0f : s_x1, s_x_rows ? nullptr : row_sel, s_w, bias,
-                           nullptr, nullptr, out, out_dtype, ldo, nullptr, 0, stream, s_x_rows, nullptr, 0, nullptr, 0, 0, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, 0, act);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x_rows ? 1.0f : s_x0; c.s_x1 = s_x_rows ? 1.0f : s_x1; c.row_sel = s_x_rows ? nullptr : row_sel; c.sx_vec = s_x_rows;
+    c.s_w = s_w; c.bias = bias; c.act = act;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_rowscale_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N,
@@ -931,12 +931,12 @@ extern "C" int mq_gemm_w4a8_rowscale_ws(const int8_t *a, long lda, const void *w
                                         const float *x0, const float *w0, void *out, int out_dtype, long ldo,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_rowscale_ws: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!s_x_rows) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_rowscale_ws: s_x_rows is required");
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, 1.0f, 1.0f, nullptr, s_w, bias, x0, w0,
-                           out, out_dtype, ldo, workspace, workspace_bytes, stream, s_x_rows);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.sx_vec = s_x_rows; c.s_w = s_w; c.bias = bias; c.x0 = x0; c.w0 = w0; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_rank2_ws(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
@@ -945,27 +945,26 @@ extern "C" int mq_gemm_w4a8_rank2_ws(const int8_t *a, long lda, const void *w, i
                                      const float *x1, const float *w1, void *out, int out_dtype, long ldo,
                                      void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_rank2_ws: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!x0 || !w0 || !x1 || !w1) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_rank2_ws: both rank-1 terms are required (one term: mq_gemm_w4a8_ws)");
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, s_x_rows ? 1.0f : s_x0, s_x_rows ? 1.0f : s_x1, s_x_rows ? nullptr : row_sel,
-                           s_w, bias, x0, w0, out, out_dtype, ldo, workspace, workspace_bytes, stream, s_x_rows, nullptr, 0,
-                           nullptr, 0, 0, x1, w1);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = s_x_rows ? 1.0f : s_x0; c.s_x1 = s_x_rows ? 1.0f : s_x1; c.row_sel = s_x_rows ? nullptr : row_sel; c.sx_vec = s_x_rows;
+    c.s_w = s_w; c.bias = bias; c.x0 = x0; c.w0 = w0; c.x1 = x1; c.w1 = w1; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_groupscale(const int8_t *a, long lda, const void *w, int w_bits, long M, long N,
                                        long K_pad, const float *s_x_groups, long n_groups, int group_k, const float *s_w,
                                        const float *bias, void *out, int out_dtype, long ldo, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!s_x_groups || n_groups <= 0) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale: s_x_groups is required");
-    if ((long)group_k * n_groups > K_pad || (long)group_k * n_groups + 127 < K_pad)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale: %ld groups of %d do not cover K_pad=%ld", n_groups, group_k, K_pad);
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, 1.0f, 1.0f, nullptr, s_w, bias, nullptr, nullptr,
-                           out, out_dtype, ldo, nullptr, 0, stream, nullptr, nullptr, 0, s_x_groups, n_groups, group_k);
+    if (const int rc = mq::check_groups_cover(__func__, n_groups, group_k, K_pad)) return rc;
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.sx_groups = s_x_groups; c.n_groups = n_groups; c.group_k = group_k; c.s_w = s_w; c.bias = bias;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_groupscale_asym(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
@@ -973,16 +972,15 @@ extern "C" int mq_gemm_w4a8_groupscale_asym(const int8_t *a, long lda, const voi
                                             long n_groups, int group_k, const float *s_w, const float *bias, void *out,
                                             int out_dtype, long ldo, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale_asym: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!s_x_groups || !shift_groups || !wsum_groups || n_groups <= 0)
         return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale_asym: s_x_groups, shift_groups and wsum_groups are required");
-    if ((long)group_k * n_groups > K_pad || (long)group_k * n_groups + 127 < K_pad)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_groupscale_asym: %ld groups of %d do not cover K_pad=%ld", n_groups, group_k, K_pad);
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, 1.0f, 1.0f, nullptr, s_w, bias, nullptr, nullptr,
-                           out, out_dtype, ldo, nullptr, 0, stream, nullptr, nullptr, 0, s_x_groups, n_groups, group_k,
-                           nullptr, nullptr, shift_groups, wsum_groups);
+    if (const int rc = mq::check_groups_cover(__func__, n_groups, group_k, K_pad)) return rc;
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.sx_groups = s_x_groups; c.n_groups = n_groups; c.group_k = group_k; c.shift_groups = shift_groups; c.wsum_groups = wsum_groups;
+    c.s_w = s_w; c.bias = bias;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
@@ -990,34 +988,32 @@ extern "C" int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w
                                         const uint8_t *row_sel, const float *s_x_rows, const float *s_x_groups,
                                         const float *bias, void *out, int out_dtype, long ldo, void *stream)
 {
-    if (out_dtype != MQ_F16 && out_dtype != MQ_BF16 && out_dtype != MQ_F32)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale: unknown output dtype %d", out_dtype);
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
     if (M == 0 || N == 0) return MQ_OK;
     if (!s_w_groups || n_groups <= 0) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale: s_w_groups is required");
-    if ((long)group_k * n_groups > K_pad || (long)group_k * n_groups + 127 < K_pad)
-        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale: %ld groups of %d do not cover K_pad=%ld", n_groups, group_k, K_pad);
+    if (const int rc = mq::check_groups_cover(__func__, n_groups, group_k, K_pad)) return rc;
     if (s_x_groups && (s_x_rows || row_sel))
         return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale: group-wise activation scales exclude per-row / per-token-type scales");
     const bool unit = s_x_groups || s_x_rows;           // the row scale is elsewhere: x 1.0 in the epilogue is exact
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, unit ? 1.0f : s_x0, unit ? 1.0f : s_x1, unit ? nullptr : row_sel, nullptr, bias,
-                           nullptr, nullptr, out, out_dtype, ldo, nullptr, 0, stream, s_x_groups ? nullptr : s_x_rows, nullptr, 0,
-                           s_x_groups, n_groups, group_k, nullptr, nullptr, nullptr, nullptr, s_w_groups);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = unit ? 1.0f : s_x0; c.s_x1 = unit ? 1.0f : s_x1; c.row_sel = unit ? nullptr : row_sel; c.sx_vec = s_x_groups ? nullptr : s_x_rows;
+    c.sx_groups = s_x_groups; c.sw_groups = s_w_groups; c.n_groups = n_groups; c.group_k = group_k; c.bias = bias;
+    return mq::gemm_common(c);
 }
 
 extern "C" int mq_gemm_w4a8_i32(const int8_t *a, long lda, const void *w, int w_bits, long M,
                                 long N, long K_pad, int32_t *acc, long ldacc, void *stream)
 {
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, 1.0f, 1.0f, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, acc, mq::EPI_I32, ldacc, nullptr, 0, stream);
+    return mq::gemm_common(mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, acc, mq::EPI_I32, ldacc, stream));
 }
 
 extern "C" int mq_gemm_w4a8_i32_ws(const int8_t *a, long lda, const void *w, int w_bits, long M,
                                    long N, long K_pad, int32_t *acc, long ldacc, void *workspace,
                                    size_t workspace_bytes, void *stream)
 {
-    return mq::gemm_common(a, lda, w, w_bits, M, N, K_pad, 1.0f, 1.0f, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, acc, mq::EPI_I32, ldacc, workspace, workspace_bytes,
-                           stream);
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, acc, mq::EPI_I32, ldacc, stream);
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return mq::gemm_common(c);
 }
 
 // TEST-ONLY hook: force a tile shape (-1 = heuristic; the ids are the cases of dispatch_tile /

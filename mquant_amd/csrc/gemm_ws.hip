@@ -1281,7 +1281,7 @@ static int launch_ws(const GemmArgs &p, hipStream_t st)
     return check_launch("gemm_ws");
 }
 
-// Activation in the store (GemmArgs::act): the 16x16x64 tiles (ids 44-48; the 32x32x32 ids 40-43 map onto their twins).
+// Activation in the store (GemmArgs::act): the 16x16x64 tiles (the 32x32x32 and the slab-free ids map onto their twins).
 template <int W_BITS, int EPI>
 static int dispatch_ws_act(const GemmArgs &p, int tile, hipStream_t st)
 {
@@ -1289,13 +1289,13 @@ static int dispatch_ws_act(const GemmArgs &p, int tile, hipStream_t st)
         return fail(MQ_EINVAL, "gemm_ws: an activation needs a floating-point output");
     } else {
         switch (tile) {
-        case 40: case 44: case 50: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, true>(p, st);
-        case 41: case 45: case 51: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1, 0, true>(p, st);
-        case 42: case 46: case 52:
+        case TILE_WS32_96x128: case TILE_WS_96x128: case TILE_WSD_96x128: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, true>(p, st);
+        case TILE_WS32_128x128: case TILE_WS_128x128: case TILE_WSD_128x128: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1, 0, true>(p, st);
+        case TILE_WS32_192x128: case TILE_WS_192x128: case TILE_WSD_192x128:
             if constexpr (W_BITS == 4) return launch_ws<192, 128, 2, 4, 4, 4, W_BITS, EPI, 1, 0, true>(p, st);
             else break;
-        case 43: case 47: case 53: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1, 0, true>(p, st);
-        case 48: case 54: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, true>(p, st);
+        case TILE_WS32_64x128: case TILE_WS_64x128: case TILE_WSD_64x128: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1, 0, true>(p, st);
+        case TILE_WS_96x128_2W: case TILE_WSD_96x128_2W: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, true>(p, st);
         default: break;
         }
         return fail(MQ_EINVAL, "gemm_ws: tile %d has no activation epilogue", tile);
@@ -1306,40 +1306,38 @@ template <int W_BITS, int EPI>
 int dispatch_ws(const GemmArgs &p, int tile, hipStream_t st)
 {
     // (QuickGELU is elementwise: the slab-free ids carry it themselves; silu(gate) * up needs the slab to bring the two halves together)
-    const bool direct_gelu = p.act == MQ_ACT_QUICK_GELU && tile >= 50 && tile <= 54 && (EPI == EPI_F16 || EPI == EPI_BF16) && p.vec_ok && p.par_ok
-                             && ((uintptr_t)p.s_w) % 16 == 0 && g_pp_act_slab == 0;
+    const bool direct_gelu = p.act == MQ_ACT_QUICK_GELU && tile_is_ws_direct(tile) && direct_epilogue_ok<EPI>(p) && g_pp_act_slab == 0;
     if (p.act != MQ_ACT_NONE && !direct_gelu) return dispatch_ws_act<W_BITS, EPI>(p, tile, st);
     switch (tile) {
     // one math wave per SIMD (1 x 4 wave tiles) or two (2 x 4), four loader waves
-    case 40: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI>(p, st);
-    case 41: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI>(p, st);
-    case 42:
+    case TILE_WS32_96x128: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI>(p, st);
+    case TILE_WS32_128x128: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI>(p, st);
+    case TILE_WS32_192x128:
         if constexpr (W_BITS == 4) return launch_ws<192, 128, 2, 4, 4, 4, W_BITS, EPI>(p, st);
         else break;
-    case 43: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI>(p, st);
+    case TILE_WS32_64x128: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI>(p, st);
     // the same tiles with V_MFMA_I32_16X16X64_I8 in the math waves (round 5)
-    case 44: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1>(p, st);
-    case 45: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1>(p, st);
-    case 46:
+    case TILE_WS_96x128: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1>(p, st);
+    case TILE_WS_128x128: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1>(p, st);
+    case TILE_WS_192x128:
         if constexpr (W_BITS == 4) return launch_ws<192, 128, 2, 4, 4, 4, W_BITS, EPI, 1>(p, st);
         else break;
-    case 47: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1>(p, st);
+    case TILE_WS_64x128: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1>(p, st);
     // 96 x 128 with TWO math waves per SIMD (48 x 32 per wave): the 16x16x64 form issues at full rate from two waves
-    case 48: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1>(p, st);
-    // ids 50-54: the 16x16x64 tiles 44-48 with the DIRECT epilogue (no LDS slab; see the kernel's head).  Plain 16-bit launches only
-    // (no split-K, residual, second rank-1 term, RoPE; aligned parameters, N % 8 == 0): anything else takes the slab twin.
-    case 50: case 51: case 52: case 53: case 54: {
-        const bool direct_ok = (EPI == EPI_F16 || EPI == EPI_BF16) && p.splits == 1 && (!p.residual || p.res_vec) && !p.x1 && !p.rope_cos && p.vec_ok
-                               && p.par_ok && ((uintptr_t)p.s_w) % 16 == 0;
-        if (!direct_ok) return dispatch_ws<W_BITS, EPI>(p, tile - 6, st);
+    case TILE_WS_96x128_2W: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1>(p, st);
+    // the 16x16x64 tiles with the DIRECT epilogue (no LDS slab; see the kernel's head).  Plain 16-bit launches only
+    // (no split-K, unaligned residual, second rank-1 term, RoPE; aligned parameters, N % 8 == 0): anything else takes the slab twin.
+    case TILE_WSD_96x128: case TILE_WSD_128x128: case TILE_WSD_192x128: case TILE_WSD_64x128: case TILE_WSD_96x128_2W: {
+        const bool direct_ok = direct_epilogue_ok<EPI>(p) && p.splits == 1 && (!p.residual || p.res_vec) && !p.x1 && !p.rope_cos;
+        if (!direct_ok) return dispatch_ws<W_BITS, EPI>(p, tile_slab_twin(tile), st);
         if constexpr (EPI == EPI_F16 || EPI == EPI_BF16) {
             switch (tile) {
-            case 50: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, false, true>(p, st);
-            case 51: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1, 0, false, true>(p, st);
-            case 52:
+            case TILE_WSD_96x128: return launch_ws<96, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, false, true>(p, st);
+            case TILE_WSD_128x128: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 4), W_BITS, EPI, 1, 0, false, true>(p, st);
+            case TILE_WSD_192x128:
                 if constexpr (W_BITS == 4) return launch_ws<192, 128, 2, 4, 4, 4, W_BITS, EPI, 1, 0, false, true>(p, st);
-                else return dispatch_ws<W_BITS, EPI>(p, 45, st);
-            case 53: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1, 0, false, true>(p, st);
+                else return dispatch_ws<W_BITS, EPI>(p, TILE_WS_128x128, st);
+            case TILE_WSD_64x128: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 8 : 6), W_BITS, EPI, 1, 0, false, true>(p, st);
             default: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, 0, false, true>(p, st);
             }
         }
@@ -1357,20 +1355,20 @@ int dispatch_ws(const GemmArgs &p, int tile, hipStream_t st)
 template <int W_BITS, int EPI, int WGM>
 static int dispatch_ws_group_mode(const GemmArgs &p, int tile, hipStream_t st)
 {
-    if (tile >= 50 && tile <= 54) tile -= 6;          // (the slab-free ids: their 16x16x64 twins carry the group fold)
-    if (tile == 46) {
+    tile = tile_slab_twin(tile);                      // (the slab-free ids: their 16x16x64 twins carry the group fold)
+    if (tile == TILE_WS_192x128) {
         // 192 x 128: twelve waves at <= 168 registers each cannot hold the extra fp32 accumulators (136 bytes of scratch).  Its shapes take
         // 128 x 128 or 96 x 128, whichever needs fewer row-rounds (gate|up: 7 x 128 against 10 x 96, measured 14-20 % ahead; ViT fc1:
         // 2 x 128 against 2 x 96, measured 15 % behind -- profiles/r5_group_gemm_ws_fold.txt)
         const long cus = device_cu_count(), nb = (p.N + 127) / 128;
         const long r128 = (((p.M + 127) / 128) * nb + cus - 1) / cus * 128, r96 = (((p.M + 95) / 96) * nb + cus - 1) / cus * 96;
-        tile = r128 < r96 ? 45 : 48;
+        tile = r128 < r96 ? TILE_WS_128x128 : TILE_WS_96x128_2W;
     }
     switch (tile) {
     // (ring depths: one stage fewer than the per-channel tiles where the scale blocks would not fit the 160 KiB)
-    case 45: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 5 : 4), W_BITS, EPI, 1, WGM>(p, st);
-    case 47: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, WGM>(p, st);
-    case 48: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 5), W_BITS, EPI, 1, WGM>(p, st);
+    case TILE_WS_128x128: return launch_ws<128, 128, 2, 4, 4, (W_BITS == 4 ? 5 : 4), W_BITS, EPI, 1, WGM>(p, st);
+    case TILE_WS_64x128: return launch_ws<64, 128, 1, 4, 4, (W_BITS == 4 ? 7 : 5), W_BITS, EPI, 1, WGM>(p, st);
+    case TILE_WS_96x128_2W: return launch_ws<96, 128, 2, 4, 4, (W_BITS == 4 ? 6 : 5), W_BITS, EPI, 1, WGM>(p, st);
     default: break;
     }
     return fail(MQ_EINVAL, "gemm_ws: tile %d has no group-scale variant", tile);

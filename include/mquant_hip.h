@@ -165,6 +165,41 @@ int mq_act_hadamard_quant_i8(const void *x, const void *x2, int act, int x_dtype
 /* TEST-ONLY hook (thread-local, not part of the drop-in surface): 256 or 512 threads per row. */
 int mq_hadamard_debug_threads(int threads);
 
+/* TEST-ONLY: everything the host decides for a launch of the exact Hadamard kernel with these arguments and the calling thread's
+ * mq_hadamard_debug_threads setting -- the launch itself is driven by the same plan.  Host arithmetic only (without a device the
+ * CU count is taken as 256).  flags: MQ_HAD_*; quant != 0: mq_hadamard_quant_i8 (act: 0 or MQ_ACT_* of mq_act_hadamard_quant_i8;
+ * tiled != 0: ldo = MQ_LD_TILED); aligned: MQ_HAD_ALIGN_* bits.  plan receives MQ_HAD_PLAN_INTS ints, indexed by MQ_HAD_PLAN_*.
+ * Returns the code (and mq_last_error the message) of the launch for shapes the launch refuses. */
+#define MQ_HAD_ALIGN_X 1    /* x (and x2): 16-byte aligned pointer and row stride, the loads are vector loads */
+#define MQ_HAD_ALIGN_Q2 2   /* row-major int8 destination: even row stride */
+#define MQ_HAD_ALIGN_Q4 4   /* row-major int8 destination: row stride a multiple of 4 (implies MQ_HAD_ALIGN_Q2) */
+#define MQ_HAD_PLAN_THREADS 0      /* 256 / 512 threads per row */
+#define MQ_HAD_PLAN_UNIT 1         /* 0, or 5 / 3: mask-driven 5 x 2 / 3 x 2 units of a prepared descriptor */
+#define MQ_HAD_PLAN_HALF_LDS 2     /* the row is staged as 16-bit values */
+#define MQ_HAD_PLAN_ACT 3          /* the fused-activation instantiation */
+#define MQ_HAD_PLAN_PARTS_LOG2 4   /* 2^parts workgroups share one row's K x K units */
+#define MQ_HAD_PLAN_GRID 5         /* workgroups */
+#define MQ_HAD_PLAN_LDS 6          /* dynamic LDS bytes */
+#define MQ_HAD_PLAN_BUTTERFLY 7    /* MQ_HAD_BF_* */
+#define MQ_HAD_PLAN_KXK 8          /* MQ_HAD_KXK_* */
+#define MQ_HAD_PLAN_REMAP 9        /* tiled output: rows handed out by the XCD row map */
+#define MQ_HAD_PLAN_FAST_FIRST 10  /* MQ_HAD_FAST: the fast dispatcher is tried first, this plan is what runs if it declines */
+#define MQ_HAD_PLAN_X_VEC 11       /* 16-byte loads of x */
+#define MQ_HAD_PLAN_Q_VEC 12       /* int8 levels stored four (two) at a time instead of byte by byte */
+#define MQ_HAD_PLAN_INTS 13
+#define MQ_HAD_BF_SCALAR 0   /* n/K < 8: scalar staging, every butterfly through LDS */
+#define MQ_HAD_BF_LANE 1     /* 8 .. 512: in-lane, DPP and shuffle butterflies */
+#define MQ_HAD_BF_REG 2      /* 1024 .. 8192: plus one register-resident pass over the staged row */
+#define MQ_HAD_BF_LDS 3      /* above: plus read-modify-write LDS passes from stride 512 */
+#define MQ_HAD_KXK_K1_VEC4 0
+#define MQ_HAD_KXK_K1_SCALAR 1
+#define MQ_HAD_KXK_CLASSIC 2 /* one 16-row tile x four column tiles per wave step, sign words */
+#define MQ_HAD_KXK_UNIT5 3
+#define MQ_HAD_KXK_UNIT3 4
+#define MQ_HAD_KXK_CHAIN 5   /* n/K < 64: scalar chain per output element */
+int mq_hadamard_debug_plan(long M, long n_in, long n, int K, int x_dtype, int flags, int quant, int act, int tiled,
+                           int aligned, int *plan);
+
 /* ---------------------------------------------------------------------------
  * Weight formats.
  * mq_pack_i4 / mq_unpack_i4: the reference wire format, quant_utils.py:61-94

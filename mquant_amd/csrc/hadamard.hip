@@ -590,43 +590,144 @@ __global__ __launch_bounds__(THREADS, HALF_LDS ? 4 : 1) void hadamard_kernel(Had
     }
 }
 
-template <int DT, bool QUANT, bool HALF_LDS, int THREADS, bool ACT = false, int UNIT = 0>
-static int launch_hadamard_t(HadArgs p, hipStream_t st)
+static thread_local int g_had_threads = 0;   // test hook (mq_hadamard_debug_threads); 0: choose by shape
+
+// ---- the launch plan: EVERY host decision of a call, made once (make_had_plan) and read by the template switch below and by
+// mq_hadamard_debug_plan.  The classes name the run-time branches of hadamard_kernel (include/mquant_hip.h MQ_HAD_BF_* / MQ_HAD_KXK_*).
+struct HadPlanIn {
+    long M, n_in, n;
+    int K, x_dtype, flags;      // flags: MQ_HAD_*
+    bool quant;
+    int act;                    // MQ_ACT_*
+    bool tiled;                 // int8 destination in the tiled layout (quant only)
+    bool x_vec;                 // x (and the row stride) allow 16-byte loads
+    int ldq_mod4;               // row stride of a row-major int8 destination modulo 4 (0 when tiled / not quantizing)
+    int hook;                   // mq_hadamard_debug_threads of the calling thread
+};
+
+struct HadPlan {
+    bool empty = false;         // M == 0: nothing to launch
+    int m = 0;
+    int threads = 256, unit = 0;          // unit: 0 = classic / chain / K == 1, 5 / 3 = mask-driven 5 x 2 / 3 x 2 units
+    bool half_lds = false, act_inst = false, masks = false, remap = false, fast_first = false, lds_over = false;
+    int unit_j = 1, unit_g = 4;
+    int parts_log2 = 0;
+    long blocks = 0;
+    size_t lds = 0;
+    int row_bytes = 0, swz = 0, y_bytes = 0;
+    int butterfly = 0, kxk = 0, q_vec = 0;
+};
+
+static int make_had_plan(const HadPlanIn &in, HadPlan &pl)
 {
-    const int esz = HALF_LDS ? 2 : 4;
-    p.row_bytes = p.m * esz;
-    p.swz = (p.K > 1 && p.row_bytes % 256 == 0) ? 1 : 0;
-    long yb = p.n * esz;
-    p.y_bytes = (int)((yb + 15) / 16 * 16);
-    const size_t wpr = (p.K + 31) / 32;
-    const size_t lds = (size_t)p.y_bytes + (p.K > 1 ? (size_t)p.K * wpr * 4 : 0);
-    if (lds > 160 * 1024) return fail(MQ_EUNSUPPORTED, "mq_hadamard: n=%ld needs %zu B of LDS (> 160 KiB)", p.n, lds);
-    auto kern = hadamard_kernel<DT, QUANT, HALF_LDS, THREADS, ACT, UNIT>;
-    {   // per device and instantiation; the first call of a shape happens outside any stream capture
-        const int rc = ensure_dynamic_lds((const void *)kern, 160 * 1024);
-        if (rc != MQ_OK) return rc;
+    pl = HadPlan{};
+    MQ_REQUIRE(in.M >= 0 && in.n > 0 && in.n_in > 0 && in.n_in <= in.n, "mq_hadamard: bad shape (n_in=%ld, n=%ld)", in.n_in, in.n);
+    if (in.M == 0) {
+        pl.empty = true;
+        return MQ_OK;
     }
-    long per_cu = (160 * 1024) / (long)lds;
+    const int K = in.K;
+    MQ_REQUIRE(K >= 1 && in.n % K == 0, "mq_hadamard: K=%d does not divide n=%ld", K, in.n);
+    const int m = pl.m = (int)(in.n / K);
+    MQ_REQUIRE((m & (m - 1)) == 0, "mq_hadamard: n/K=%d is not a power of two", m);
+    MQ_REQUIRE(K == 1 || K % 4 == 0, "mq_hadamard: K=%d needs 4-byte aligned had_words and K %% 4 == 0", K);
+    MQ_REQUIRE(in.act == MQ_ACT_NONE || m >= 8, "mq_act_hadamard_quant_i8: n/K must be >= 8");
+    pl.fast_first = (in.flags & MQ_HAD_FAST) != 0;
+    const int JT = (K + 15) / 16;
+    if ((in.flags & MQ_HAD_PREPARED) && K > 1) {
+        // measured (profiles/r2_hadamard.txt): the 5 x 2 units pay off for the large factors (K = 140 / 156 /
+        // 172, down_proj 76 -> 72 us); for small K the round-1 form (one tile x four column tiles) is faster
+        // measured (profiles/r2_hadamard.txt, r4_hadamard_cu_timeline.txt): mask-driven units pay off where a row splits into
+        // exactly ONE unit per wave (wave w of every resident workgroup runs on the same SIMD, so uneven shares pile up there):
+        // 5 x 2 units for K = 140 / 156 with m = 128 (eight waves), 3 x 2 units for K = 172 with m = 64 (eight waves) and for the
+        // vision tower's 40 x 128 (four waves); everything else keeps the round-1 form (one tile x four column tiles)
+        const int u5 = ((JT + 4) / 5) * (m / 32), u3 = ((JT + 2) / 3) * (m / 32);
+        if (m >= 64 && m % 32 == 0 && JT >= 8 && u5 == 8) {
+            pl.masks = true;
+            pl.unit_j = 5;
+            pl.unit_g = 2;
+        } else if (m >= 64 && m % 32 == 0 && (u3 == 8 || u3 == 4)) {
+            pl.masks = true;
+            pl.unit_j = 3;
+            pl.unit_g = 2;
+        }
+    }
+    // 16-bit staging is exact only when the scaled butterflies are rounded to x's dtype AND no
+    // later butterfly pass runs through LDS (m <= 512, m >= 8)
+    pl.half_lds = in.x_dtype != MQ_F32 && !(in.flags & MQ_HAD_FP32) && m >= 8 && m <= 512;
+    // 8 waves per row pay off once the K x K stage has enough (16 rows x 64 columns) units to
+    // keep them busy (down_proj: 10 x 2 = 20 units; measured 83 -> 76 us), else 4 waves
+    int units = (K > 1 && m >= 64) ? JT * (m / 64) : 0;
+    pl.threads = in.hook ? in.hook : (units >= 16 ? 512 : 256);
+    if (pl.masks) {                                 // mask-driven units: one unit per wave where possible
+        units = pl.unit_j == 5 ? ((JT + 4) / 5) * (m / 32) : ((JT + 2) / 3) * (m / 32);
+        if (!in.hook) pl.threads = units >= 8 ? 512 : 256;
+        if (pl.unit_j == 5 && pl.threads == 512) pl.unit = 5;
+        if (pl.unit_j == 3 && ((pl.threads == 256 && units == 4) || (pl.threads == 512 && units == 8))) pl.unit = 3;
+    }
+    // the units store two int8 levels at a time (had_kxk_unit): every row of a row-major destination starts on an even byte
+    MQ_REQUIRE(!(in.quant && pl.unit != 0 && (in.ldq_mod4 & 1)),
+               "mq_hadamard_quant_i8: a prepared descriptor's %d x 2 units need an even row stride of the int8 output", pl.unit);
+    pl.act_inst = in.quant && in.act != MQ_ACT_NONE;
+    pl.remap = in.quant && in.tiled && in.M >= 128;
+
+    const int esz = pl.half_lds ? 2 : 4;
+    const long yb = (in.n * esz + 15) / 16 * 16;
+    pl.lds = (size_t)yb + (K > 1 ? (size_t)K * ((K + 31) / 32) * 4 : 0);
+    pl.butterfly = m < 8 ? MQ_HAD_BF_SCALAR : m <= 512 ? MQ_HAD_BF_LANE : m <= 8192 ? MQ_HAD_BF_REG : MQ_HAD_BF_LDS;
+    pl.q_vec = in.quant ? (in.ldq_mod4 == 0) : 0;   // four (two) levels per store instead of single bytes
+    pl.kxk = K == 1 ? (((in.n & 3) == 0 && (!in.quant || in.ldq_mod4 == 0)) ? MQ_HAD_KXK_K1_VEC4 : MQ_HAD_KXK_K1_SCALAR)
+             : pl.unit == 5 ? MQ_HAD_KXK_UNIT5 : pl.unit == 3 ? MQ_HAD_KXK_UNIT3 : m >= 64 ? MQ_HAD_KXK_CLASSIC : MQ_HAD_KXK_CHAIN;
+    if (pl.lds > 160 * 1024) {
+        pl.lds_over = true;                         // reported by had_plan_refusal, after the fast dispatcher had its try
+        return MQ_OK;
+    }
+    pl.row_bytes = m * esz;
+    pl.swz = (K > 1 && pl.row_bytes % 256 == 0) ? 1 : 0;
+    pl.y_bytes = (int)yb;
+    long per_cu = (160 * 1024) / (long)pl.lds;
     if (per_cu > 8) per_cu = 8;
 #ifndef MQ_HAD_GRID_BY_LDS
     // Only as many workgroups as are RESIDENT (16-bit staging: 16 waves per CU, the kernel's launch bounds): the row loop
     // hands a workgroup its next row the moment it is done, whereas a workgroup dispatched into a freed slot started
     // 15 k cycles later (profiles/r4_hadamard_cu_timeline.txt)
-    if (HALF_LDS && per_cu > 16 / (THREADS / 64)) per_cu = 16 / (THREADS / 64);
+    if (pl.half_lds && per_cu > 16 / (pl.threads / 64)) per_cu = 16 / (pl.threads / 64);
 #endif
     if (per_cu < 1) per_cu = 1;
     long blocks = (long)device_cu_count() * per_cu;
-    p.parts_log2 = 0;
-    if ((UNIT == 5 || UNIT == 3) && QUANT && p.M < 128) {
+    if (pl.unit != 0 && in.quant && in.M < 128) {
         // short batch: share a row's units among workgroups while a CU is still free (units per row: a power of two here)
-        const int JT = (p.K + 15) / 16, units = ((JT + UNIT - 1) / UNIT) * (p.m / 32);
-        while ((2 << p.parts_log2) <= units && units % (2 << p.parts_log2) == 0 && (p.M << (p.parts_log2 + 1)) <= device_cu_count()) ++p.parts_log2;
+        while ((2 << pl.parts_log2) <= units && units % (2 << pl.parts_log2) == 0 && (in.M << (pl.parts_log2 + 1)) <= device_cu_count()) ++pl.parts_log2;
     }
     // (with the row map the VIRTUAL rows count: 130 rows are 256 virtual ones, and 136 workgroups would walk two of them each)
-    const long vrows = (QUANT && p.ldq == MQ_LD_TILED && p.M >= 128) ? ceil_div(p.M, 128) * 128 : (p.M << p.parts_log2);
+    const long vrows = pl.remap ? ceil_div(in.M, 128) * 128 : (in.M << pl.parts_log2);
     if (blocks > vrows) blocks = vrows;
-    if (QUANT && p.ldq == MQ_LD_TILED) blocks = ceil_div(blocks, 8) * 8;   // XCD-consistent row map (tiled_row_of)
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), lds, st, p);
+    if (in.quant && in.tiled) blocks = ceil_div(blocks, 8) * 8;   // XCD-consistent row map (tiled_row_of)
+    pl.blocks = blocks;
+    return MQ_OK;
+}
+
+static int had_plan_refusal(long n, const HadPlan &pl)
+{
+    if (pl.lds_over) return fail(MQ_EUNSUPPORTED, "mq_hadamard: n=%ld needs %zu B of LDS (> 160 KiB)", n, pl.lds);
+    return MQ_OK;
+}
+
+template <int DT, bool QUANT, bool HALF_LDS, int THREADS, bool ACT = false, int UNIT = 0>
+static int launch_hadamard_t(HadArgs p, const HadPlan &pl, hipStream_t st)
+{
+    if (pl.threads != THREADS || pl.unit != UNIT || pl.half_lds != HALF_LDS || pl.act_inst != ACT)
+        return fail(MQ_EINVAL, "mq_hadamard: the launch switch left its plan");
+    p.row_bytes = pl.row_bytes;
+    p.swz = pl.swz;
+    p.y_bytes = pl.y_bytes;
+    p.parts_log2 = pl.parts_log2;
+    auto kern = hadamard_kernel<DT, QUANT, HALF_LDS, THREADS, ACT, UNIT>;
+    {   // per device and instantiation; the first call of a shape happens outside any stream capture
+        const int rc = ensure_dynamic_lds((const void *)kern, 160 * 1024);
+        if (rc != MQ_OK) return rc;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.blocks), dim3(THREADS), pl.lds, st, p);
     return check_launch("hadamard");
 }
 
@@ -670,91 +771,64 @@ __global__ __launch_bounds__(64) void hadamard_prepare_kernel(const unsigned *wo
     }
 }
 
-static thread_local int g_had_threads = 0;   // test hook (mq_hadamard_debug_threads); 0: choose by shape
-
 template <int DT, bool QUANT, bool HALF_LDS>
-static int launch_hadamard(const HadArgs &p, hipStream_t st)
+static int launch_hadamard(const HadArgs &p, const HadPlan &pl, hipStream_t st)
 {
-    // 8 waves per row pay off once the K x K stage has enough (16 rows x 64 columns) units to
-    // keep them busy (down_proj: 10 x 2 = 20 units; measured 83 -> 76 us), else 4 waves
-    int units = (p.K > 1 && p.m >= 64) ? ((p.K + 15) / 16) * (p.m / 64) : 0;
-    int threads = g_had_threads ? g_had_threads : (units >= 16 ? 512 : 256);
-    if (p.masks && p.K > 1 && p.m >= 64) {          // mask-driven units: one unit per wave where possible
-        const int JT = (p.K + 15) / 16;
-        units = p.unit_j == 5 ? ((JT + 4) / 5) * (p.m / 32) : p.unit_j == 3 ? ((JT + 2) / 3) * (p.m / 32) : JT * (p.m / 64);
-        if (!g_had_threads) threads = units >= 8 ? 512 : 256;
+    const bool unit5 = pl.unit == 5;
+    const bool unit3 = pl.unit == 3 && pl.threads == 256;
+    const bool unit3w = pl.unit == 3 && pl.threads == 512;
+    if (QUANT && pl.act_inst) {
+        if (unit5) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT, 5>(p, pl, st);
+        if (unit3) return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, QUANT, 3>(p, pl, st);
+        if (unit3w) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT, 3>(p, pl, st);
+        if (pl.threads == 512) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT>(p, pl, st);
+        return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, QUANT>(p, pl, st);
     }
-    const bool unit5 = p.masks && p.unit_j == 5 && threads == 512;
-    const bool unit3 = p.masks && p.unit_j == 3 && threads == 256 && units == 4;
-    const bool unit3w = p.masks && p.unit_j == 3 && threads == 512 && units == 8;
-    if (QUANT && p.act != MQ_ACT_NONE) {
-        if (unit5) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT, 5>(p, st);
-        if (unit3) return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, QUANT, 3>(p, st);
-        if (unit3w) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT, 3>(p, st);
-        if (threads == 512) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, QUANT>(p, st);
-        return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, QUANT>(p, st);
-    }
-    if (unit5) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, false, 5>(p, st);
-    if (unit3) return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, false, 3>(p, st);
-    if (unit3w) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, false, 3>(p, st);
-    if (threads == 512) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512>(p, st);
-    return launch_hadamard_t<DT, QUANT, HALF_LDS, 256>(p, st);
+    if (unit5) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, false, 5>(p, pl, st);
+    if (unit3) return launch_hadamard_t<DT, QUANT, HALF_LDS, 256, false, 3>(p, pl, st);
+    if (unit3w) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512, false, 3>(p, pl, st);
+    if (pl.threads == 512) return launch_hadamard_t<DT, QUANT, HALF_LDS, 512>(p, pl, st);
+    return launch_hadamard_t<DT, QUANT, HALF_LDS, 256>(p, pl, st);
 }
 
 template <int DT, bool QUANT>
-static int launch_hadamard_dt(const HadArgs &p, hipStream_t st)
+static int launch_hadamard_dt(const HadArgs &p, const HadPlan &pl, hipStream_t st)
 {
-    // 16-bit staging is exact only when the scaled butterflies are rounded to x's dtype AND no
-    // later butterfly pass runs through LDS (m <= 512, m >= 8)
-    const bool half_ok = (DT != MQ_F32) && !p.fp32_had && p.m >= 8 && p.m <= 512;
-    if (DT != MQ_F32 && half_ok) return launch_hadamard<DT, QUANT, (DT != MQ_F32)>(p, st);
-    return launch_hadamard<DT, QUANT, false>(p, st);
+    if (DT != MQ_F32 && pl.half_lds) return launch_hadamard<DT, QUANT, (DT != MQ_F32)>(p, pl, st);
+    return launch_hadamard<DT, QUANT, false>(p, pl, st);
 }
 
 static int hadamard_common(HadArgs p, int x_dtype, bool quant, void *stream)
 {
-    MQ_REQUIRE(p.M >= 0 && p.n > 0 && p.n_in > 0 && p.n_in <= p.n, "mq_hadamard: bad shape (n_in=%ld, n=%ld)", p.n_in, p.n);
-    if (p.M == 0) return MQ_OK;
-    MQ_REQUIRE(p.K >= 1 && p.n % p.K == 0, "mq_hadamard: K=%d does not divide n=%ld", p.K, p.n);
-    p.m = (int)(p.n / p.K);
-    p.inv_sqrt_n = 1.0f / sqrtf((float)p.n);
-    MQ_REQUIRE((p.m & (p.m - 1)) == 0, "mq_hadamard: n/K=%d is not a power of two", p.m);
-    MQ_REQUIRE(p.K == 1 || (p.K % 4 == 0 && p.had_bits && ((uintptr_t)p.had_bits) % 4 == 0), "mq_hadamard: K=%d needs 4-byte aligned had_words and K %% 4 == 0", p.K);
     // fp32_had carries flags: bit 0 = --fp32_had, bit 1 = had_words is a prepared descriptor (mq_hadamard_prepare),
     // bit 2 = THIS call may take the non-default fast K x K stage (MQ_HAD_FAST)
-    const bool prepared = (p.fp32_had & MQ_HAD_PREPARED) != 0;
-    const bool fast = (p.fp32_had & MQ_HAD_FAST) != 0;
-    p.fp32_had &= MQ_HAD_FP32;
-    p.masks = nullptr;
-    p.hfrag = nullptr;
-    p.unit_j = 1; p.unit_g = 4;
-    if (prepared && p.K > 1) {
-        MQ_REQUIRE(((uintptr_t)p.had_bits) % 16 == 0, "mq_hadamard: a prepared descriptor is 16-byte aligned");
-        p.masks = reinterpret_cast<const unsigned long long *>(p.had_bits + prepared_masks_offset(p.K));
-        if (x_dtype != MQ_F32)
-            p.hfrag = reinterpret_cast<const v4i *>(p.had_bits + prepared_half_offset(p.K) + (x_dtype == MQ_BF16 ? prepared_half_bytes(p.K) : 0));
-        const int JT = (p.K + 15) / 16;
-        // measured (profiles/r2_hadamard.txt): the 5 x 2 units pay off for the large factors (K = 140 / 156 /
-        // 172, down_proj 76 -> 72 us); for small K the round-1 form (one tile x four column tiles) is faster
-        // measured (profiles/r2_hadamard.txt, r4_hadamard_cu_timeline.txt): mask-driven units pay off where a row splits into
-        // exactly ONE unit per wave (wave w of every resident workgroup runs on the same SIMD, so uneven shares pile up there):
-        // 5 x 2 units for K = 140 / 156 with m = 128 (eight waves), 3 x 2 units for K = 172 with m = 64 (eight waves) and for the
-        // vision tower's 40 x 128 (four waves); everything else keeps the round-1 form (one tile x four column tiles)
-        const int u5 = ((JT + 4) / 5) * (p.m / 32), u3 = ((JT + 2) / 3) * (p.m / 32);
-        if (p.m >= 64 && p.m % 32 == 0 && JT >= 8 && u5 == 8) {
-            p.unit_j = 5;
-            p.unit_g = 2;
-        } else if (p.m >= 64 && p.m % 32 == 0 && (u3 == 8 || u3 == 4)) {
-            p.unit_j = 3;
-            p.unit_g = 2;
-        } else {
-            p.masks = nullptr;
-        }
-    }
-    MQ_REQUIRE(p.ldx >= p.n_in, "mq_hadamard: ldx < n_in");
+    const int flags = p.fp32_had;
     const size_t esz = (x_dtype == MQ_F32) ? 4 : 2;
     p.vec_ok = (((uintptr_t)p.x) % 16 == 0) && ((p.ldx * esz) % 16 == 0);
     p.vec_ok2 = p.x2 && (((uintptr_t)p.x2) % 16 == 0) && ((p.ldx * esz) % 16 == 0);
+    const bool tiled = quant && p.ldq == MQ_LD_TILED;
+    HadPlan pl;   // every decision of this launch (shape refusals included): the switch below only reads it
+    {
+        const HadPlanIn in{p.M, p.n_in, p.n, p.K, x_dtype, flags, quant, p.act, tiled, p.vec_ok != 0,
+                           (quant && !tiled) ? (int)(p.ldq & 3) : 0, g_had_threads};
+        const int rc = make_had_plan(in, pl);
+        if (rc != MQ_OK) return rc;
+    }
+    if (pl.empty) return MQ_OK;
+    p.m = pl.m;
+    p.inv_sqrt_n = 1.0f / sqrtf((float)p.n);
+    MQ_REQUIRE(p.K == 1 || (p.had_bits && ((uintptr_t)p.had_bits) % 4 == 0), "mq_hadamard: K=%d needs 4-byte aligned had_words and K %% 4 == 0", p.K);
+    p.fp32_had = flags & MQ_HAD_FP32;
+    p.masks = nullptr;
+    p.hfrag = nullptr;
+    p.unit_j = pl.unit_j; p.unit_g = pl.unit_g;
+    if ((flags & MQ_HAD_PREPARED) && p.K > 1) {
+        MQ_REQUIRE(((uintptr_t)p.had_bits) % 16 == 0, "mq_hadamard: a prepared descriptor is 16-byte aligned");
+        if (pl.masks) p.masks = reinterpret_cast<const unsigned long long *>(p.had_bits + prepared_masks_offset(p.K));
+        if (x_dtype != MQ_F32)
+            p.hfrag = reinterpret_cast<const v4i *>(p.had_bits + prepared_half_offset(p.K) + (x_dtype == MQ_BF16 ? prepared_half_bytes(p.K) : 0));
+    }
+    MQ_REQUIRE(p.ldx >= p.n_in, "mq_hadamard: ldx < n_in");
     hipStream_t st = (hipStream_t)stream;
     if (quant) {
         MQ_REQUIRE(p.qout && p.K_pad >= p.n && (p.ldq == MQ_LD_TILED ? p.K_pad % 64 == 0 : p.ldq >= p.K_pad),
@@ -764,22 +838,25 @@ static int hadamard_common(HadArgs p, int x_dtype, bool quant, void *stream)
     } else {
         MQ_REQUIRE(p.out && p.ldo >= p.n, "mq_hadamard: bad output geometry");
     }
-    if (fast) {              // non-default per-call flag MQ_HAD_FAST: K x K stage on the half-precision matrix core
+    if (pl.fast_first) {     // non-default per-call flag MQ_HAD_FAST: K x K stage on the half-precision matrix core
         const int rc = hadamard_fast_dispatch(p, x_dtype, quant, st);
         if (rc != MQ_EUNSUPPORTED) return rc;
     }
+    if (x_dtype == MQ_F16 || x_dtype == MQ_BF16 || x_dtype == MQ_F32) {
+        const int rc = had_plan_refusal(p.n, pl);
+        if (rc != MQ_OK) return rc;
+    }
     if (quant) {
         switch (x_dtype) {
-        case MQ_F16: return launch_hadamard_dt<MQ_F16, true>(p, st);
-        case MQ_BF16: return launch_hadamard_dt<MQ_BF16, true>(p, st);
-        case MQ_F32: return launch_hadamard_dt<MQ_F32, true>(p, st);
+        case MQ_F16: return launch_hadamard_dt<MQ_F16, true>(p, pl, st);
+        case MQ_BF16: return launch_hadamard_dt<MQ_BF16, true>(p, pl, st);
+        case MQ_F32: return launch_hadamard_dt<MQ_F32, true>(p, pl, st);
         }
     } else {
-        MQ_REQUIRE(p.out && p.ldo >= p.n, "mq_hadamard: bad output geometry");
         switch (x_dtype) {
-        case MQ_F16: return launch_hadamard_dt<MQ_F16, false>(p, st);
-        case MQ_BF16: return launch_hadamard_dt<MQ_BF16, false>(p, st);
-        case MQ_F32: return launch_hadamard_dt<MQ_F32, false>(p, st);
+        case MQ_F16: return launch_hadamard_dt<MQ_F16, false>(p, pl, st);
+        case MQ_BF16: return launch_hadamard_dt<MQ_BF16, false>(p, pl, st);
+        case MQ_F32: return launch_hadamard_dt<MQ_F32, false>(p, pl, st);
         }
     }
     return fail(MQ_EINVAL, "mq_hadamard: unknown dtype %d", x_dtype);
@@ -809,6 +886,39 @@ extern "C" int mq_hadamard_debug_threads(int threads)
 {
     // TEST-ONLY: 256 / 512 threads per row for the calling thread's later launches; 0: by shape
     mq::g_had_threads = (threads == 512 || threads == 256) ? threads : 0;
+    return MQ_OK;
+}
+
+extern "C" int mq_hadamard_debug_plan(long M, long n_in, long n, int K, int x_dtype, int flags, int quant, int act, int tiled,
+                                      int aligned, int *plan)
+{
+    // TEST-ONLY: what a launch with these arguments (and the calling thread's mq_hadamard_debug_threads) decides; no device work
+    using namespace mq;
+    MQ_REQUIRE(plan != nullptr, "mq_hadamard_debug_plan: plan is null");
+    if (x_dtype != MQ_F16 && x_dtype != MQ_BF16 && x_dtype != MQ_F32) return fail(MQ_EINVAL, "mq_hadamard: unknown dtype %d", x_dtype);
+    MQ_REQUIRE(quant || (act == MQ_ACT_NONE && !tiled), "mq_hadamard_debug_plan: act / tiled belong to the quantizing entry points");
+    const bool row_major_q = quant && !tiled;
+    const HadPlanIn in{M, n_in, n, K, x_dtype, flags, quant != 0, act, quant && tiled, (aligned & MQ_HAD_ALIGN_X) != 0,
+                       !row_major_q ? 0 : (aligned & MQ_HAD_ALIGN_Q4) ? 0 : (aligned & MQ_HAD_ALIGN_Q2) ? 2 : 1, g_had_threads};
+    HadPlan pl;
+    int rc = make_had_plan(in, pl);
+    if (rc == MQ_OK) rc = had_plan_refusal(n, pl);
+    if (rc != MQ_OK) return rc;
+    for (int i = 0; i < MQ_HAD_PLAN_INTS; ++i) plan[i] = 0;
+    if (pl.empty) return MQ_OK;
+    plan[MQ_HAD_PLAN_THREADS] = pl.threads;
+    plan[MQ_HAD_PLAN_UNIT] = pl.unit;
+    plan[MQ_HAD_PLAN_HALF_LDS] = pl.half_lds;
+    plan[MQ_HAD_PLAN_ACT] = pl.act_inst;
+    plan[MQ_HAD_PLAN_PARTS_LOG2] = pl.parts_log2;
+    plan[MQ_HAD_PLAN_GRID] = (int)pl.blocks;
+    plan[MQ_HAD_PLAN_LDS] = (int)pl.lds;
+    plan[MQ_HAD_PLAN_BUTTERFLY] = pl.butterfly;
+    plan[MQ_HAD_PLAN_KXK] = pl.kxk;
+    plan[MQ_HAD_PLAN_REMAP] = pl.remap;
+    plan[MQ_HAD_PLAN_FAST_FIRST] = pl.fast_first;
+    plan[MQ_HAD_PLAN_X_VEC] = in.x_vec;
+    plan[MQ_HAD_PLAN_Q_VEC] = pl.q_vec;
     return MQ_OK;
 }
 
@@ -845,7 +955,6 @@ extern "C" int mq_act_hadamard_quant_i8(const void *x, const void *x2, int act, 
     if (M == 0) return MQ_OK;                       // empty input: nothing to do (null pointers allowed)
     MQ_REQUIRE(act == MQ_ACT_SILU_MUL || act == MQ_ACT_QUICK_GELU, "mq_act_hadamard_quant_i8: unknown activation %d", act);
     MQ_REQUIRE(act != MQ_ACT_SILU_MUL || x2 != nullptr, "mq_act_hadamard_quant_i8: silu(gate)*up needs the second operand");
-    MQ_REQUIRE(K >= 1 && n % K == 0 && n / K >= 8, "mq_act_hadamard_quant_i8: n/K must be >= 8");
     HadArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.x2 = x2; p.act = act;

@@ -4,7 +4,7 @@
 // 16-byte store, rows are walked by a grid-stride loop.
 //
 // Reference semantics: fake_quant/quantizer/uniform.py:20-43, base.py:44-50.
-#include "mq_common.h"
+#include "act_quant_common.h"
 
 namespace mq {
 
@@ -45,27 +45,7 @@ __global__ __launch_bounds__(256) void act_quant_kernel(
         const T *xr = x + row * ldx + col;
 
         float v[16];
-        if (col + 16 <= K && vec_ok) {
-            if (sizeof(T) == 2) {
-                const v8us a = *reinterpret_cast<const v8us *>(xr);
-                const v8us b = *reinterpret_cast<const v8us *>(xr + 8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    v[i] = Elem<DT>::ld((T)a[i]);
-                    v[8 + i] = Elem<DT>::ld((T)b[i]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v4f a = *reinterpret_cast<const v4f *>((const float *)xr + 4 * j);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[4 * j + i] = a[i];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = (col + i < K) ? Elem<DT>::ld(xr[i]) : 0.0f;
-        }
+        load_chunk16<DT>(xr, col, K, vec_ok, v);
 
         int q[16];
         if (sv) {
@@ -85,13 +65,7 @@ __global__ __launch_bounds__(256) void act_quant_kernel(
         }
 
         if (!DEQUANT) {
-            int8_t *out = reinterpret_cast<int8_t *>(out_) + act_offset(row, col, K_pad, ldo);
-            v4i p;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                p[j] = (q[4 * j] & 0xff) | ((q[4 * j + 1] & 0xff) << 8) |
-                       ((q[4 * j + 2] & 0xff) << 16) | ((q[4 * j + 3] & 0xff) << 24);
-            *reinterpret_cast<v4i *>(out) = p;
+            store_levels16(reinterpret_cast<int8_t *>(out_), row, col, K_pad, ldo, q);
         } else {
             T *out = reinterpret_cast<T *>(out_) + row * ldo + col;
 #pragma unroll
@@ -195,7 +169,7 @@ static int launch_act_quant(const void *x, long M, long K, long ldx, float scale
     typedef typename Elem<DT>::T T;
     const long total = ((!DEQUANT && ldo == MQ_LD_TILED) ? ((M + 15) / 16) * 16 : M) * (K_pad / 16);
     if (total == 0) return MQ_OK;
-    const int vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * (long)sizeof(T)) % 16 == 0);
+    const int vec_ok = rows_vec_ok(x, ldx, DT);
 #ifdef MQ_AQ_GENERIC_ONLY   // A/B builds (tools/bench_ab.sh): everything on the general kernel, as before round 4
     const bool own_kernel = false;
 #else
@@ -236,13 +210,10 @@ extern "C" int mq_quantize_act_i8(const void *x, int x_dtype, long M, long K, lo
     MQ_REQUIRE(ldx >= K, "mq_quantize_act_i8: ldx < K");
     MQ_REQUIRE(!row_sel || !scale_vec0 || scale_vec1, "mq_quantize_act_i8: row_sel with per-channel scales needs scale_vec1");
     if (!scale_vec1) scale_vec1 = scale_vec0;
-    hipStream_t st = (hipStream_t)stream;
-    switch (x_dtype) {
-    case MQ_F16: return launch_act_quant<MQ_F16, false>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, x0_out, out, K_pad, ldo, st);
-    case MQ_BF16: return launch_act_quant<MQ_BF16, false>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, x0_out, out, K_pad, ldo, st);
-    case MQ_F32: return launch_act_quant<MQ_F32, false>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, x0_out, out, K_pad, ldo, st);
-    }
-    return fail(MQ_EINVAL, "mq_quantize_act_i8: unknown dtype %d", x_dtype);
+    return with_dtype(__func__, x_dtype, [&](auto dt) {
+        return launch_act_quant<decltype(dt)::value, false>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, x0_out,
+                                                            out, K_pad, ldo, (hipStream_t)stream);
+    });
 }
 
 extern "C" int mq_fakequant_act(const void *x, int x_dtype, long M, long K, long ldx,
@@ -257,11 +228,8 @@ extern "C" int mq_fakequant_act(const void *x, int x_dtype, long M, long K, long
     MQ_REQUIRE(ldx >= K && ldo >= K, "mq_fakequant_act: leading dimension < K");
     if (!scale_vec1) scale_vec1 = scale_vec0;
     const long K_pad = ceil_div(K, 16) * 16;
-    hipStream_t st = (hipStream_t)stream;
-    switch (x_dtype) {
-    case MQ_F16: return launch_act_quant<MQ_F16, true>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, nullptr, out, K_pad, ldo, st);
-    case MQ_BF16: return launch_act_quant<MQ_BF16, true>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, nullptr, out, K_pad, ldo, st);
-    case MQ_F32: return launch_act_quant<MQ_F32, true>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, nullptr, out, K_pad, ldo, st);
-    }
-    return fail(MQ_EINVAL, "mq_fakequant_act: unknown dtype %d", x_dtype);
+    return with_dtype(__func__, x_dtype, [&](auto dt) {
+        return launch_act_quant<decltype(dt)::value, true>(x, M, K, ldx, scale0, scale1, scale_vec0, scale_vec1, row_sel, skip_col0, nullptr,
+                                                           out, K_pad, ldo, (hipStream_t)stream);
+    });
 }

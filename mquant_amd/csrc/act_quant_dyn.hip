@@ -7,7 +7,7 @@
 // One workgroup per row, the row stays in registers between the max pass and the quantize pass.
 // skip_col0 (ActQuantWrapper.split, :367-372): column 0 is excluded from the range, comes back in
 // x0_out as fp32 and gets level 0.
-#include "mq_common.h"
+#include "act_quant_common.h"
 
 namespace mq {
 
@@ -46,28 +46,7 @@ __global__ __launch_bounds__(DQ_THREADS) void act_quant_dyn_kernel(DqArgs p)
         const long ch = t + (long)c * DQ_THREADS;
         if (ch < chunks) {
             const long col = ch * 16;
-            const T *src = xr + col;
-            if (col + 16 <= p.K && p.vec_ok) {
-                if (sizeof(T) == 2) {
-                    const v8us a = *reinterpret_cast<const v8us *>(src);
-                    const v8us b = *reinterpret_cast<const v8us *>(src + 8);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        v[c][i] = Elem<DT>::ld((T)a[i]);
-                        v[c][8 + i] = Elem<DT>::ld((T)b[i]);
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const v4f a = *reinterpret_cast<const v4f *>((const float *)src + 4 * j);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) v[c][4 * j + i] = a[i];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) v[c][i] = (col + i < p.K) ? Elem<DT>::ld(src[i]) : 0.0f;
-            }
+            load_chunk16<DT>(xr + col, col, p.K, p.vec_ok, v[c]);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 if (p.skip_col0 && col + i == 0) continue;
@@ -93,29 +72,13 @@ __global__ __launch_bounds__(DQ_THREADS) void act_quant_dyn_kernel(DqArgs p)
     // maxq tensor does not promote): range * clip, the scale, the zero point, x / scale and the level sum are 16-bit
     // tensors for a half model, each torch op rounding its fp32 result once.  The per-token rule promotes to fp32 (:239).
     const bool faithful = (DT != MQ_F32) && p.range_in != nullptr;
-    auto rd = [&](float v) { return faithful ? Elem<DT>::rnd(v) : v; };
-    float xmin = rd(mn * p.clip), xmax0 = rd(mx * p.clip);
-    float s, zero = 0.0f, lo, hi;
-    if (ASYM) {                                         // quant_utils.py:255-268 + asym_quant :27-31
-        if (p.range_in) {                               // the per-tensor rule fixes each bound on its own (:229-232)
-            if (xmin == 0.0f) xmin = -1.0f;
-            if (xmax0 == 0.0f) xmax0 = 1.0f;
-        } else if (xmin == 0.0f && xmax0 == 0.0f) { xmin = -1.0f; xmax0 = 1.0f; }
-        s = rd(rd(xmax0 - xmin) / p.maxq);
-        zero = rintf(rd(-xmin / s));
-        lo = 0.0f;
-        hi = p.maxq;
-        if (t == 0) {
-            if (p.scale_out) p.scale_out[row] = s;
-            if (p.zero_out) p.zero_out[row] = zero;
-            if (p.shift_out) p.shift_out[row] = s * (p.half - zero);
+    const QuantRange r = quant_range<DT, ASYM>(mn, mx, p.clip, p.maxq, faithful, /*each_bound=*/p.range_in != nullptr);
+    if (t == 0) {
+        if (p.scale_out) p.scale_out[row] = r.scale;
+        if (ASYM) {                                     // quant_utils.py:255-268 + asym_quant :27-31
+            if (p.zero_out) p.zero_out[row] = r.zero;
+            if (p.shift_out) p.shift_out[row] = r.scale * (p.half - r.zero);
         }
-    } else {
-        const float xmax = fmaxf(fabsf(xmin), xmax0);
-        s = (xmax == 0.0f) ? 1.0f : rd(xmax / p.maxq);
-        if (t == 0 && p.scale_out) p.scale_out[row] = s;
-        lo = -(p.maxq + 1.0f);
-        hi = p.maxq;
     }
 
 #pragma unroll
@@ -125,31 +88,40 @@ __global__ __launch_bounds__(DQ_THREADS) void act_quant_dyn_kernel(DqArgs p)
             int q[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                if (ASYM) {      // clamp(rint(x / s) + zero, 0, maxq), stored minus 2^(bits-1); pad columns 0 (their weights are 0)
-                    float lv = rd(rintf(rd(v[c][i] / s)) + zero);
-                    lv = fminf(fmaxf(lv, lo), hi);
-                    q[i] = (ch * 16 + i < p.K) ? (int)(lv - p.half) : 0;
-                } else if (faithful) {
-                    const float lv = fminf(fmaxf(rintf(Elem<DT>::rnd(v[c][i] / s)), lo), hi);
-                    q[i] = (ch * 16 + i < p.K) ? (int)lv : 0;
-                } else {
-                    q[i] = (ch * 16 + i < p.K) ? quant_level(v[c][i], s, lo, hi) : 0;
-                }
+                const int lv = range_level<DT, ASYM>(v[c][i], r, p.half, faithful);
+                q[i] = (ch * 16 + i < p.K) ? lv : 0;      // pad columns 0 (their weights are 0)
             }
             if (p.skip_col0 && ch == 0) {
                 if (p.x0_out) p.x0_out[row] = v[c][0];
                 q[0] = 0;
             }
-            v4i pk;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                pk[j] = (q[4 * j] & 0xff) | ((q[4 * j + 1] & 0xff) << 8) | ((q[4 * j + 2] & 0xff) << 16) |
-                        ((q[4 * j + 3] & 0xff) << 24);
-            *reinterpret_cast<v4i *>(p.out + act_offset(row, ch * 16, p.K_pad, p.ldo)) = pk;
+            store_levels16(p.out, row, ch * 16, p.K_pad, p.ldo, q);
         }
     }
-    for (long k = chunks * 16 + t * 16L; k < p.K_pad; k += DQ_THREADS * 16L)
-        *reinterpret_cast<v4i *>(p.out + act_offset(row, k, p.K_pad, p.ldo)) = v4i{0, 0, 0, 0};
+    zero_row_tail<DQ_THREADS>(p.out, row, chunks * 16, p.K_pad, p.ldo, t);
+}
+
+// The three per-token entry points after their own argument checks: the checks they share (in fn's name), the argument block,
+// the launch.  asym: levels 0 .. 2^bits - 1 stored minus 2^(bits-1), zero points and shifts out; range_in: the per-tensor mode.
+static int quantize_act_rows(const char *fn, const void *x, int x_dtype, long M, long K, long ldx, int bits, float clip_ratio, bool asym,
+                             int skip_col0, const float *range_in, float *x0_out, float *scale_out, float *zero_out,
+                             float *shift_out, int8_t *out, long K_pad, long ldo, void *stream)
+{
+    MQ_REQUIRE(bits >= 2 && bits <= 8, "%s: bits must be 2..8", fn);
+    MQ_REQUIRE(K <= 16L * DQ_THREADS * DQ_MAX_CHUNKS, "%s: K=%ld too large (max %d)", fn, K, 16 * DQ_THREADS * DQ_MAX_CHUNKS);
+    if (const int rc = check_act_dest(fn, out, K, K_pad, ldo)) return rc;
+    DqArgs p;
+    p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.clip = clip_ratio;
+    p.maxq = asym ? (float)((1 << bits) - 1) : (float)((1 << (bits - 1)) - 1);
+    p.half = asym ? (float)(1 << (bits - 1)) : 0.0f;
+    p.skip_col0 = skip_col0; p.x0_out = x0_out; p.scale_out = scale_out; p.zero_out = zero_out; p.shift_out = shift_out;
+    p.range_in = range_in; p.out = out; p.K_pad = K_pad; p.ldo = ldo;
+    p.vec_ok = rows_vec_ok(x, ldx, x_dtype);
+    return with_dtype_asym(fn, x_dtype, asym, [&](auto dt, auto as) {
+        hipLaunchKernelGGL((act_quant_dyn_kernel<decltype(dt)::value, decltype(as)::value>), dim3((unsigned)M), dim3(DQ_THREADS), 0,
+                           (hipStream_t)stream, p);
+        return check_launch(fn + 3);                    // the name without its mq_
+    });
 }
 
 }  // namespace mq
@@ -158,29 +130,10 @@ extern "C" int mq_quantize_act_dyn_i8(const void *x, int x_dtype, long M, long K
                                       float clip_ratio, int skip_col0, float *x0_out, float *scale_out,
                                       int8_t *out, long K_pad, long ldo, void *stream)
 {
-    using namespace mq;
     if (M == 0) return MQ_OK;                       // empty input: nothing to do (null pointers allowed)
     MQ_REQUIRE(x && out && scale_out && M >= 0 && K > 0 && ldx >= K, "mq_quantize_act_dyn_i8: bad shape");
-    MQ_REQUIRE(bits >= 2 && bits <= 8, "mq_quantize_act_dyn_i8: bits must be 2..8");
-    MQ_REQUIRE(K <= 16L * DQ_THREADS * DQ_MAX_CHUNKS, "mq_quantize_act_dyn_i8: K=%ld too large (max %d)", K, 16 * DQ_THREADS * DQ_MAX_CHUNKS);
-    MQ_REQUIRE(K_pad >= K && K_pad % 16 == 0 && ((uintptr_t)out) % 16 == 0 &&
-                   (ldo == MQ_LD_TILED ? K_pad % 64 == 0 : (ldo >= K_pad && ldo % 16 == 0)),
-               "mq_quantize_act_dyn_i8: bad K_pad / ldo / alignment");
-    if (M == 0) return MQ_OK;
-    DqArgs p;
-    p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.clip = clip_ratio; p.maxq = (float)((1 << (bits - 1)) - 1);
-    p.skip_col0 = skip_col0; p.x0_out = x0_out; p.scale_out = scale_out; p.out = out; p.K_pad = K_pad; p.ldo = ldo;
-    p.zero_out = nullptr; p.shift_out = nullptr; p.half = 0.0f; p.range_in = nullptr;
-    const size_t esz = (x_dtype == MQ_F32) ? 4 : 2;
-    p.vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * esz) % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    switch (x_dtype) {
-    case MQ_F16: hipLaunchKernelGGL(act_quant_dyn_kernel<MQ_F16>, dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    case MQ_BF16: hipLaunchKernelGGL(act_quant_dyn_kernel<MQ_BF16>, dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    case MQ_F32: hipLaunchKernelGGL(act_quant_dyn_kernel<MQ_F32>, dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    default: return fail(MQ_EINVAL, "mq_quantize_act_dyn_i8: unknown dtype %d", x_dtype);
-    }
-    return check_launch("quantize_act_dyn_i8");
+    return mq::quantize_act_rows(__func__, x, x_dtype, M, K, ldx, bits, clip_ratio, false, skip_col0, nullptr, x0_out, scale_out,
+                                 nullptr, nullptr, out, K_pad, ldo, stream);
 }
 
 /* Dynamic ASYMMETRIC per-token quantizer (--a_asym without --*_static; quant_utils.py:239-268 else-branch):
@@ -193,29 +146,10 @@ extern "C" int mq_quantize_act_dyn_asym_i8(const void *x, int x_dtype, long M, l
                                            float clip_ratio, float *scale_out, float *zero_out, float *shift_out,
                                            int8_t *out, long K_pad, long ldo, void *stream)
 {
-    using namespace mq;
     if (M == 0) return MQ_OK;
     MQ_REQUIRE(x && out && scale_out && shift_out && M >= 0 && K > 0 && ldx >= K, "mq_quantize_act_dyn_asym_i8: bad shape");
-    MQ_REQUIRE(bits >= 2 && bits <= 8, "mq_quantize_act_dyn_asym_i8: bits must be 2..8");
-    MQ_REQUIRE(K <= 16L * DQ_THREADS * DQ_MAX_CHUNKS, "mq_quantize_act_dyn_asym_i8: K=%ld too large (max %d)", K, 16 * DQ_THREADS * DQ_MAX_CHUNKS);
-    MQ_REQUIRE(K_pad >= K && K_pad % 16 == 0 && ((uintptr_t)out) % 16 == 0 &&
-                   (ldo == MQ_LD_TILED ? K_pad % 64 == 0 : (ldo >= K_pad && ldo % 16 == 0)),
-               "mq_quantize_act_dyn_asym_i8: bad K_pad / ldo / alignment");
-    DqArgs p;
-    p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.clip = clip_ratio; p.maxq = (float)((1 << bits) - 1);
-    p.half = (float)(1 << (bits - 1));
-    p.skip_col0 = 0; p.x0_out = nullptr; p.scale_out = scale_out; p.zero_out = zero_out; p.shift_out = shift_out; p.range_in = nullptr;
-    p.out = out; p.K_pad = K_pad; p.ldo = ldo;
-    const size_t esz = (x_dtype == MQ_F32) ? 4 : 2;
-    p.vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * esz) % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    switch (x_dtype) {
-    case MQ_F16: hipLaunchKernelGGL((act_quant_dyn_kernel<MQ_F16, true>), dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    case MQ_BF16: hipLaunchKernelGGL((act_quant_dyn_kernel<MQ_BF16, true>), dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    case MQ_F32: hipLaunchKernelGGL((act_quant_dyn_kernel<MQ_F32, true>), dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); break;
-    default: return fail(MQ_EINVAL, "mq_quantize_act_dyn_asym_i8: unknown dtype %d", x_dtype);
-    }
-    return check_launch("quantize_act_dyn_asym_i8");
+    return mq::quantize_act_rows(__func__, x, x_dtype, M, K, ldx, bits, clip_ratio, true, 0, nullptr, nullptr, scale_out, zero_out,
+                                 shift_out, out, K_pad, ldo, stream);
 }
 
 /* Dynamic PER-TENSOR quantizer (act_per_tensor = True; quant_utils.py:214-237): the range of the whole
@@ -228,37 +162,11 @@ extern "C" int mq_quantize_act_range_i8(const void *x, int x_dtype, long M, long
                                         float *x0_out, float *scale_out, float *zero_out, float *shift_out,
                                         int8_t *out, long K_pad, long ldo, void *stream)
 {
-    using namespace mq;
     if (M == 0) return MQ_OK;
     MQ_REQUIRE(x && out && scale_out && minmax && M >= 0 && K > 0 && ldx >= K, "mq_quantize_act_range_i8: bad shape");
     MQ_REQUIRE(!asym || (shift_out && !skip_col0), "mq_quantize_act_range_i8: the asymmetric mode needs shift_out and no split column");
-    MQ_REQUIRE(bits >= 2 && bits <= 8, "mq_quantize_act_range_i8: bits must be 2..8");
-    MQ_REQUIRE(K <= 16L * DQ_THREADS * DQ_MAX_CHUNKS, "mq_quantize_act_range_i8: K=%ld too large (max %d)", K, 16 * DQ_THREADS * DQ_MAX_CHUNKS);
-    MQ_REQUIRE(K_pad >= K && K_pad % 16 == 0 && ((uintptr_t)out) % 16 == 0 &&
-                   (ldo == MQ_LD_TILED ? K_pad % 64 == 0 : (ldo >= K_pad && ldo % 16 == 0)),
-               "mq_quantize_act_range_i8: bad K_pad / ldo / alignment");
-    DqArgs p;
-    p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.clip = clip_ratio;
-    p.maxq = asym ? (float)((1 << bits) - 1) : (float)((1 << (bits - 1)) - 1);
-    p.half = asym ? (float)(1 << (bits - 1)) : 0.0f;
-    p.skip_col0 = skip_col0; p.x0_out = x0_out; p.scale_out = scale_out; p.zero_out = zero_out; p.shift_out = shift_out;
-    p.range_in = minmax; p.out = out; p.K_pad = K_pad; p.ldo = ldo;
-    const size_t esz = (x_dtype == MQ_F32) ? 4 : 2;
-    p.vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * esz) % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-#define MQ_DQ_LAUNCH(DT)                                                                                              \
-    do {                                                                                                              \
-        if (asym) hipLaunchKernelGGL((act_quant_dyn_kernel<DT, true>), dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p); \
-        else hipLaunchKernelGGL((act_quant_dyn_kernel<DT, false>), dim3((unsigned)M), dim3(DQ_THREADS), 0, st, p);    \
-    } while (0)
-    switch (x_dtype) {
-    case MQ_F16: MQ_DQ_LAUNCH(MQ_F16); break;
-    case MQ_BF16: MQ_DQ_LAUNCH(MQ_BF16); break;
-    case MQ_F32: MQ_DQ_LAUNCH(MQ_F32); break;
-    default: return fail(MQ_EINVAL, "mq_quantize_act_range_i8: unknown dtype %d", x_dtype);
-    }
-#undef MQ_DQ_LAUNCH
-    return check_launch("quantize_act_range_i8");
+    return mq::quantize_act_rows(__func__, x, x_dtype, M, K, ldx, bits, clip_ratio, asym != 0, skip_col0, minmax, x0_out, scale_out,
+                                 zero_out, shift_out, out, K_pad, ldo, stream);
 }
 
 /* Dynamic symmetric GROUP-WISE quantizer (--a_groupsize g; quant_utils.py:181-203 + sym_quant :46-50): one scale
@@ -297,26 +205,8 @@ __global__ __launch_bounds__(256) void act_quant_group_kernel(GqArgs p)
         const long cc = live ? c : total - 1;
         const long row = cc / cpr;
         const long col = (cc - row * cpr) * 16;
-        const T *xr = reinterpret_cast<const T *>(p.x) + row * p.ldx + col;
         float v[16];
-        if (col + 16 <= p.K && p.vec_ok) {
-            if (sizeof(T) == 2) {
-                const v8us a = *reinterpret_cast<const v8us *>(xr);
-                const v8us b = *reinterpret_cast<const v8us *>(xr + 8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { v[i] = Elem<DT>::ld((T)a[i]); v[8 + i] = Elem<DT>::ld((T)b[i]); }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v4f a = *reinterpret_cast<const v4f *>((const float *)xr + 4 * j);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[4 * j + i] = a[i];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = (col + i < p.K) ? Elem<DT>::ld(xr[i]) : 0.0f;
-        }
+        load_chunk16<DT>(reinterpret_cast<const T *>(p.x) + row * p.ldx + col, col, p.K, p.vec_ok, v);
         float mn = v[0], mx = v[0];
 #pragma unroll
         for (int i = 1; i < 16; ++i) { mn = fminf(mn, v[i]); mx = fmaxf(mx, v[i]); }
@@ -324,96 +214,67 @@ __global__ __launch_bounds__(256) void act_quant_group_kernel(GqArgs p)
             mn = fminf(mn, __shfl_xor(mn, st, 64));
             mx = fmaxf(mx, __shfl_xor(mx, st, 64));
         }
-        float xmin = Elem<DT>::rnd(mn * p.clip), xmax0 = Elem<DT>::rnd(mx * p.clip);
-        float s, z = 0.0f;
-        if (ASYM) {      // quant_utils.py:181-203, sym = False: the range is [amin, amax] * clip (0 need not be inside), (-1, +1) when both are 0
-            if (xmin == 0.0f && xmax0 == 0.0f) { xmin = -1.0f; xmax0 = 1.0f; }
-            s = Elem<DT>::rnd(Elem<DT>::rnd(xmax0 - xmin) / p.maxq);
-            z = rintf(Elem<DT>::rnd(-xmin / s));
-        } else {
-            const float xmax = fmaxf(fabsf(xmin), xmax0);
-            s = (xmax == 0.0f) ? 1.0f : Elem<DT>::rnd(xmax / p.maxq);
-        }
+        // sym = False: the range is [amin, amax] * clip (0 need not be inside), (-1, +1) when both are 0
+        const QuantRange r = quant_range<DT, ASYM>(mn, mx, p.clip, p.maxq, /*round_dt=*/true, /*each_bound=*/false);
         if (!live) continue;
         const long chunk = cc - row * cpr;
         if ((chunk % p.lanes_per_group) == 0 && col < p.K) {
             const long gi = row * p.n_groups + chunk / p.lanes_per_group;
-            p.scale_out[gi] = s;
+            p.scale_out[gi] = r.scale;
             if (ASYM) {
-                if (p.zero_out) p.zero_out[gi] = z;
-                p.shift_out[gi] = s * (p.half - z);
+                if (p.zero_out) p.zero_out[gi] = r.zero;
+                p.shift_out[gi] = r.scale * (p.half - r.zero);
             }
         }
         int q[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            float t = rintf(Elem<DT>::rnd(v[i] / s));
-            if (ASYM) {
-                t = Elem<DT>::rnd(t + z);
-                t = fminf(fmaxf(t, 0.0f), p.maxq) - p.half;        // stored for the int8 GEMM: q - 2^(bits-1)
-            } else {
-                t = fminf(fmaxf(t, -(p.maxq + 1.0f)), p.maxq);
-            }
-            q[i] = (col + i < p.K) ? (int)t : 0;
+            const int lv = range_level<DT, ASYM>(v[i], r, p.half, true);
+            q[i] = (col + i < p.K) ? lv : 0;
         }
-        v4i pk;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            pk[j] = (q[4 * j] & 0xff) | ((q[4 * j + 1] & 0xff) << 8) | ((q[4 * j + 2] & 0xff) << 16) | ((q[4 * j + 3] & 0xff) << 24);
-        *reinterpret_cast<v4i *>(p.out + act_offset(row, col, p.K_pad, p.ldo)) = pk;
+        store_levels16(p.out, row, col, p.K_pad, p.ldo, q);
     }
 }
-
-}  // namespace mq
 
 static int quantize_act_group(const void *x, int x_dtype, long M, long K, long ldx, int groupsize, int bits, float clip_ratio,
                               bool asym, float *scale_out, float *zero_out, float *shift_out, int8_t *out, long K_pad, long ldo,
                               void *stream)
 {
-    using namespace mq;
+    const char *fn = "mq_quantize_act_group_i8";        // both entry points speak in the symmetric one's name
     if (M == 0) return MQ_OK;
     MQ_REQUIRE(x && out && scale_out && (!asym || shift_out) && M >= 0 && K > 0 && ldx >= K, "mq_quantize_act_group_i8: bad shape");
     MQ_REQUIRE(bits >= 2 && bits <= 8, "mq_quantize_act_group_i8: bits must be 2..8");
     MQ_REQUIRE(groupsize >= 16 && groupsize <= 1024 && (groupsize & (groupsize - 1)) == 0 && K % groupsize == 0,
                "mq_quantize_act_group_i8: groupsize=%d must be a power of two in 16..1024 that divides K=%ld", groupsize, K);
-    MQ_REQUIRE(K_pad >= K && K_pad % 16 == 0 && (K_pad / 16) % (groupsize / 16) == 0 && ((uintptr_t)out) % 16 == 0 &&
-                   (ldo == MQ_LD_TILED ? K_pad % 64 == 0 : (ldo >= K_pad && ldo % 16 == 0)),
-               "mq_quantize_act_group_i8: bad K_pad / ldo / alignment (K_pad must hold whole groups)");
+    if (const int rc = check_act_dest(fn, out, K, K_pad, ldo, "bad K_pad / ldo / alignment (K_pad must hold whole groups)", groupsize))
+        return rc;
     GqArgs p;
     p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.lanes_per_group = groupsize / 16; p.clip = clip_ratio;
     p.maxq = asym ? (float)((1 << bits) - 1) : (float)((1 << (bits - 1)) - 1);
     p.half = (float)(1 << (bits - 1));
     p.zero_out = zero_out; p.shift_out = shift_out;
     p.scale_out = scale_out; p.n_groups = K / groupsize; p.out = out; p.K_pad = K_pad; p.ldo = ldo;
-    const size_t esz = (x_dtype == MQ_F32) ? 4 : 2;
-    p.vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * esz) % 16 == 0);
+    p.vec_ok = rows_vec_ok(x, ldx, x_dtype);
     long blocks = ceil_div(M * (K_pad / 16), 256);
     if (blocks > 256L * 16) blocks = 256L * 16;
-    hipStream_t st = (hipStream_t)stream;
-#define MQ_GQ_LAUNCH(DTC) \
-    do { \
-        if (asym) hipLaunchKernelGGL((act_quant_group_kernel<DTC, true>), dim3((unsigned)blocks), dim3(256), 0, st, p); \
-        else hipLaunchKernelGGL((act_quant_group_kernel<DTC, false>), dim3((unsigned)blocks), dim3(256), 0, st, p); \
-    } while (0)
-    switch (x_dtype) {
-    case MQ_F16: MQ_GQ_LAUNCH(MQ_F16); break;
-    case MQ_BF16: MQ_GQ_LAUNCH(MQ_BF16); break;
-    case MQ_F32: MQ_GQ_LAUNCH(MQ_F32); break;
-    default: return fail(MQ_EINVAL, "mq_quantize_act_group_i8: unknown dtype %d", x_dtype);
-    }
-#undef MQ_GQ_LAUNCH
-    return check_launch("quantize_act_group_i8");
+    return with_dtype_asym(fn, x_dtype, asym, [&](auto dt, auto as) {
+        hipLaunchKernelGGL((act_quant_group_kernel<decltype(dt)::value, decltype(as)::value>), dim3((unsigned)blocks), dim3(256), 0,
+                           (hipStream_t)stream, p);
+        return check_launch("quantize_act_group_i8");
+    });
 }
+
+}  // namespace mq
 
 extern "C" int mq_quantize_act_group_i8(const void *x, int x_dtype, long M, long K, long ldx, int groupsize, int bits,
                                         float clip_ratio, float *scale_out, int8_t *out, long K_pad, long ldo, void *stream)
 {
-    return quantize_act_group(x, x_dtype, M, K, ldx, groupsize, bits, clip_ratio, false, scale_out, nullptr, nullptr, out, K_pad, ldo, stream);
+    return mq::quantize_act_group(x, x_dtype, M, K, ldx, groupsize, bits, clip_ratio, false, scale_out, nullptr, nullptr, out, K_pad, ldo, stream);
 }
 
 extern "C" int mq_quantize_act_group_asym_i8(const void *x, int x_dtype, long M, long K, long ldx, int groupsize, int bits,
                                              float clip_ratio, float *scale_out, float *zero_out, float *shift_out, int8_t *out,
                                              long K_pad, long ldo, void *stream)
 {
-    return quantize_act_group(x, x_dtype, M, K, ldx, groupsize, bits, clip_ratio, true, scale_out, zero_out, shift_out, out, K_pad, ldo, stream);
+    return mq::quantize_act_group(x, x_dtype, M, K, ldx, groupsize, bits, clip_ratio, true, scale_out, zero_out, shift_out, out, K_pad, ldo, stream);
 }

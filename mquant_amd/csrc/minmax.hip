@@ -4,7 +4,7 @@
 // Per-channel: thread t owns 8 adjacent channels (one 16-byte load per row for half
 // inputs), blockIdx.y slices the rows; slices are merged with order-independent integer
 // atomics on the fp32 bit patterns, so the result does not depend on scheduling.
-#include "mq_common.h"
+#include "act_quant_common.h"
 
 namespace mq {
 
@@ -131,23 +131,13 @@ extern "C" int mq_minmax_channels(const void *x, int x_dtype, long M, long C, lo
     const long rows_per_slice = ceil_div(M, slices);
     slices = ceil_div(M, rows_per_slice);
     const dim3 g(gx, (unsigned)slices), b(256);
-    switch (x_dtype) {
-    case MQ_F16: {
-        const int vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * 2) % 16 == 0);
-        hipLaunchKernelGGL(minmax_channels_kernel<MQ_F16>, g, b, 0, st, (const unsigned short *)x, M, C, ldx, col_begin, rows_per_slice, mn, mx, vec_ok);
-        break;
-    }
-    case MQ_BF16: {
-        const int vec_ok = (((uintptr_t)x) % 16 == 0) && ((ldx * 2) % 16 == 0);
-        hipLaunchKernelGGL(minmax_channels_kernel<MQ_BF16>, g, b, 0, st, (const unsigned short *)x, M, C, ldx, col_begin, rows_per_slice, mn, mx, vec_ok);
-        break;
-    }
-    case MQ_F32:
-        hipLaunchKernelGGL(minmax_channels_kernel<MQ_F32>, g, b, 0, st, (const float *)x, M, C, ldx, col_begin, rows_per_slice, mn, mx, 0);
-        break;
-    default: return fail(MQ_EINVAL, "mq_minmax_channels: unknown dtype %d", x_dtype);
-    }
-    return check_launch("minmax_channels");
+    const int vec_ok = rows_vec_ok(x, ldx, x_dtype);                // (the fp32 kernel has no 16-byte path and ignores it)
+    return with_dtype(__func__, x_dtype, [&](auto dt) {
+        typedef typename Elem<decltype(dt)::value>::T T;
+        hipLaunchKernelGGL(minmax_channels_kernel<decltype(dt)::value>, g, b, 0, st, (const T *)x, M, C, ldx, col_begin, rows_per_slice, mn, mx,
+                           vec_ok);
+        return check_launch("minmax_channels");
+    });
 }
 
 extern "C" int mq_minmax_tensor(const void *x, int x_dtype, long M, long C, long ldx,
@@ -162,11 +152,9 @@ extern "C" int mq_minmax_tensor(const void *x, int x_dtype, long M, long C, long
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     const dim3 g((unsigned)blocks), b(256);
-    switch (x_dtype) {
-    case MQ_F16: hipLaunchKernelGGL(minmax_tensor_kernel<MQ_F16>, g, b, 0, st, (const unsigned short *)x, M, C, ldx, col_begin, out2); break;
-    case MQ_BF16: hipLaunchKernelGGL(minmax_tensor_kernel<MQ_BF16>, g, b, 0, st, (const unsigned short *)x, M, C, ldx, col_begin, out2); break;
-    case MQ_F32: hipLaunchKernelGGL(minmax_tensor_kernel<MQ_F32>, g, b, 0, st, (const float *)x, M, C, ldx, col_begin, out2); break;
-    default: return fail(MQ_EINVAL, "mq_minmax_tensor: unknown dtype %d", x_dtype);
-    }
-    return check_launch("minmax_tensor");
+    return with_dtype(__func__, x_dtype, [&](auto dt) {
+        typedef typename Elem<decltype(dt)::value>::T T;
+        hipLaunchKernelGGL(minmax_tensor_kernel<decltype(dt)::value>, g, b, 0, st, (const T *)x, M, C, ldx, col_begin, out2);
+        return check_launch("minmax_tensor");
+    });
 }

@@ -12,7 +12,7 @@
 // bf16 path rounds to bf16 like the torch ops do) a FIXED order that the oracle restates (orc_rmsn): thread t adds the squares of its 16-element
 // chunks c = t, t + 256, ... in ascending k; XOR butterfly (1..32) inside each wave; the four wave
 // sums left to right.  1/sqrt with correctly rounded sqrt and divide (torch's CPU rsqrt).
-#include "mq_common.h"
+#include "act_quant_common.h"
 
 namespace mq {
 
@@ -50,23 +50,7 @@ __global__ __launch_bounds__(RQ_THREADS) void rmsn_quant_kernel(RqArgs p)
     for (int c = 0; c < RQ_MAX_CHUNKS; ++c) {
         const long ch = t + (long)c * RQ_THREADS;
         if (ch < chunks) {
-            const T *src = xr + ch * 16;
-            if (sizeof(T) == 2) {
-                const v8us a = *reinterpret_cast<const v8us *>(src);
-                const v8us b = *reinterpret_cast<const v8us *>(src + 8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    v[c][i] = Elem<DT>::ld((T)a[i]);
-                    v[c][8 + i] = Elem<DT>::ld((T)b[i]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v4f a = *reinterpret_cast<const v4f *>((const float *)src + 4 * j);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[c][4 * j + i] = a[i];
-                }
-            }
+            load_chunk16<DT, /*TAIL=*/false>(xr + ch * 16, ch * 16, p.K, 1, v[c]);     // whole aligned chunks only (checked by the host)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float sq = v[c][i] * v[c][i];
@@ -103,12 +87,7 @@ __global__ __launch_bounds__(RQ_THREADS) void rmsn_quant_kernel(RqArgs p)
 #pragma unroll
             for (int i = 0; i < 16; ++i) y[i] = Elem<DT>::rnd(v[c][i] * inv);
             quant_levels<16>(y, s, s_inv, s_rcp, -128.0f, 127.0f, q);      // the IEEE quotient only next to a half-integer (mq_common.h)
-            v4i pk;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                pk[j] = (q[4 * j] & 0xff) | ((q[4 * j + 1] & 0xff) << 8) | ((q[4 * j + 2] & 0xff) << 16) |
-                        ((q[4 * j + 3] & 0xff) << 24);
-            *reinterpret_cast<v4i *>(p.out + act_offset(row, ch * 16, p.K_pad, p.ldo)) = pk;
+            store_levels16(p.out, row, ch * 16, p.K_pad, p.ldo, q);
             if (p.y) {
                 T *yd = reinterpret_cast<T *>(p.y) + row * p.ldy + ch * 16;
 #pragma unroll
@@ -116,9 +95,7 @@ __global__ __launch_bounds__(RQ_THREADS) void rmsn_quant_kernel(RqArgs p)
             }
         }
     }
-    // zero the K .. K_pad tail of the int8 row (the GEMM reads whole 128-byte k-steps)
-    for (long k = p.K + t * 16L; k < p.K_pad; k += RQ_THREADS * 16L)
-        *reinterpret_cast<v4i *>(p.out + act_offset(row, k, p.K_pad, p.ldo)) = v4i{0, 0, 0, 0};
+    zero_row_tail<RQ_THREADS>(p.out, row, p.K, p.K_pad, p.ldo, t);
 }
 
 }  // namespace mq
@@ -132,24 +109,17 @@ extern "C" int mq_rmsn_quantize_i8(const void *x, int x_dtype, long M, long K, l
     MQ_REQUIRE(x && out && M >= 0 && K > 0 && ldx >= K, "mq_rmsn_quantize_i8: bad shape");
     MQ_REQUIRE(K % 16 == 0 && K <= 16L * RQ_THREADS * RQ_MAX_CHUNKS,
                "mq_rmsn_quantize_i8: K must be a multiple of 16 and <= %d (got %ld)", 16 * RQ_THREADS * RQ_MAX_CHUNKS, K);
-    MQ_REQUIRE(K_pad >= K && K_pad % 16 == 0 && (ldo == MQ_LD_TILED ? K_pad % 64 == 0 : (ldo >= K_pad && ldo % 16 == 0)),
-               "mq_rmsn_quantize_i8: bad K_pad / ldo");
+    if (const int rc = check_act_dest(__func__, out, K, K_pad, ldo, "bad K_pad / ldo")) return rc;
     MQ_REQUIRE(!y_out || ldy >= K, "mq_rmsn_quantize_i8: ldy < K");
     MQ_REQUIRE(scale0 > 0.0f && mean_dim > 0.0f, "mq_rmsn_quantize_i8: scale and mean_dim must be positive");
-    MQ_REQUIRE(((uintptr_t)x) % 16 == 0 && (ldx * (x_dtype == MQ_F32 ? 4 : 2)) % 16 == 0,
-               "mq_rmsn_quantize_i8: x rows must be 16-byte aligned");
-    if (M == 0) return MQ_OK;
+    MQ_REQUIRE(rows_vec_ok(x, ldx, x_dtype), "mq_rmsn_quantize_i8: x rows must be 16-byte aligned");
     RqArgs p;
     p.x = x; p.M = M; p.K = K; p.ldx = ldx; p.mean_dim = mean_dim; p.eps = eps;
     p.scale0 = scale0; p.scale1 = row_sel ? scale1 : scale0; p.row_sel = row_sel;
     p.y = y_out; p.ldy = ldy; p.out = out; p.K_pad = K_pad; p.ldo = ldo;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(ldo == MQ_LD_TILED ? ceil_div(M, 128) * 128 : M);      // tiled: whole groups of 8 XCDs x 16 rows
-    switch (x_dtype) {
-    case MQ_F16: hipLaunchKernelGGL(rmsn_quant_kernel<MQ_F16>, dim3(grid), dim3(RQ_THREADS), 0, st, p); break;
-    case MQ_F32: hipLaunchKernelGGL(rmsn_quant_kernel<MQ_F32>, dim3(grid), dim3(RQ_THREADS), 0, st, p); break;
-    case MQ_BF16: hipLaunchKernelGGL(rmsn_quant_kernel<MQ_BF16>, dim3(grid), dim3(RQ_THREADS), 0, st, p); break;
-    default: return fail(MQ_EINVAL, "mq_rmsn_quantize_i8: unknown dtype %d", x_dtype);
-    }
-    return check_launch("rmsn_quantize_i8");
+    return with_dtype(__func__, x_dtype, [&](auto dt) {
+        hipLaunchKernelGGL(rmsn_quant_kernel<decltype(dt)::value>, dim3(grid), dim3(RQ_THREADS), 0, (hipStream_t)stream, p);
+        return check_launch("rmsn_quantize_i8");
+    });
 }

@@ -5,7 +5,7 @@
 //     y[m][n] = ((acc * s_x) * s_w[n]) + bias[n] + (s_x * sum_k a[m][k]) * (s_w[n] (2^(b-1) - z_w[n]))
 // and the GEMM's x0 / w0 slot takes the two factors.  out[m] = s_x(m) * float(sum_k a[m][k]); the integer
 // sum is exact, one rounding in the product.  One wave per row, 16 bytes per lane per access.
-#include "mq_common.h"
+#include "act_quant_common.h"
 
 namespace mq {
 
@@ -86,14 +86,10 @@ extern "C" int mq_rank1_add_cast(const float *y32, long M, long N, long ldy, con
     R1Args p{y32, M, N, ldy, x, w, out, ldo};
     long blocks = ceil_div(M * ((N + 3) / 4), 256);
     if (blocks > 4096) blocks = 4096;
-    hipStream_t st = (hipStream_t)stream;
-    switch (out_dtype) {
-    case MQ_F16: hipLaunchKernelGGL(rank1_add_cast_kernel<MQ_F16>, dim3((unsigned)blocks), dim3(256), 0, st, p); break;
-    case MQ_BF16: hipLaunchKernelGGL(rank1_add_cast_kernel<MQ_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, p); break;
-    case MQ_F32: hipLaunchKernelGGL(rank1_add_cast_kernel<MQ_F32>, dim3((unsigned)blocks), dim3(256), 0, st, p); break;
-    default: return fail(MQ_EINVAL, "mq_rank1_add_cast: unknown dtype %d", out_dtype);
-    }
-    return check_launch("rank1_add_cast");
+    return with_dtype(__func__, out_dtype, [&](auto dt) {
+        hipLaunchKernelGGL(rank1_add_cast_kernel<decltype(dt)::value>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+        return check_launch("rank1_add_cast");
+    });
 }
 
 extern "C" int mq_act_rowsum_scaled(const int8_t *a, long lda, long M, long K_pad, float s_x0, float s_x1,
@@ -102,8 +98,7 @@ extern "C" int mq_act_rowsum_scaled(const int8_t *a, long lda, long M, long K_pa
     using namespace mq;
     if (M == 0) return MQ_OK;
     MQ_REQUIRE(a && out && M > 0 && K_pad > 0 && K_pad % 16 == 0, "mq_act_rowsum_scaled: bad shape");
-    MQ_REQUIRE(((uintptr_t)a) % 16 == 0 && (lda == MQ_LD_TILED ? K_pad % 64 == 0 : (lda >= K_pad && lda % 16 == 0)),
-               "mq_act_rowsum_scaled: bad lda / alignment");
+    if (const int rc = check_act_dest(__func__, a, K_pad, K_pad, lda, "bad lda / alignment")) return rc;
     RsArgs p{a, M, K_pad, lda, s_x0, s_x1, row_sel, s_x_rows, out};
     hipLaunchKernelGGL(act_rowsum_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("act_rowsum_scaled");

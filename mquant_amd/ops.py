@@ -147,6 +147,21 @@ def _rows(x: torch.Tensor) -> torch.Tensor:
     return x2
 
 
+def _quant_prologue(x: torch.Tensor, out, tiled: bool, *others):
+    """What every quantizer wrapper starts with: x as rows, the device check (``others``: the optional operands), the
+    destination.  Returns (x2, M, K, out, out pointer, K_pad, ldo)."""
+    x2 = _rows(x)
+    _need_cuda(x2, *others, out)
+    M, K = x2.shape
+    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    return x2, M, K, out, optr, K_pad, ldo
+
+
+def _second(scale0: float, scale1: Optional[float]) -> float:
+    """The scale of the rows that ``row_sel`` marks; one scale serves both kinds of row when it is not given."""
+    return float(scale0 if scale1 is None else scale1)
+
+
 # --------------------------------------------------------------------------- quantizer
 @_on_device
 def quantize_act_i8(x: torch.Tensor, scale0: float = 1.0, scale1: Optional[float] = None, *,
@@ -156,14 +171,11 @@ def quantize_act_i8(x: torch.Tensor, scale0: float = 1.0, scale1: Optional[float
                     out=None, x0_out: Optional[torch.Tensor] = None, tiled: bool = False):
     """fp -> int8 levels, [M, K] -> [M, ceil128(K)] (pad columns are zero); ``tiled`` (or a
     ``TiledAct`` destination) selects the layout the GEMM streams fastest."""
-    x2 = _rows(x)
-    _need_cuda(x2, scale_vec0, scale_vec1, row_sel, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled, scale_vec0, scale_vec1, row_sel)
     if skip_col0 and x0_out is None:
         x0_out = torch.empty((M,), dtype=torch.float32, device=x.device)
     call("mq_quantize_act_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0),
-         float(scale0), float(scale0 if scale1 is None else scale1),
+         float(scale0), _second(scale0, scale1),
          _ptr(scale_vec0), _ptr(scale_vec1), _ptr(row_sel), int(skip_col0), _ptr(x0_out),
          optr, K_pad, ldo, _stream())
     return out, x0_out
@@ -175,13 +187,10 @@ def rmsn_quantize_i8(x: torch.Tensor, mean_dim: float, eps: float, scale0: float
                      out=None, want_y: bool = False, tiled: bool = False):
     """Weight-less RMS norm (module_util.RMSN) + static int8 quantizer in one pass.
     Returns (int8 [M, ceil128(K)] or TiledAct, normalised activations in x's dtype | None)."""
-    x2 = _rows(x)
-    _need_cuda(x2, row_sel, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled, row_sel)
     y = torch.empty((M, K), dtype=x.dtype, device=x.device) if want_y else None
     call("mq_rmsn_quantize_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0), float(mean_dim),
-         float(eps), float(scale0), float(scale0 if scale1 is None else scale1), _ptr(row_sel),
+         float(eps), float(scale0), _second(scale0, scale1), _ptr(row_sel),
          _ptr(y), K, optr, K_pad, ldo, _stream())
     return out, (y.reshape(x.shape) if want_y else None)
 
@@ -197,7 +206,7 @@ def fakequant_act(x: torch.Tensor, scale0: float = 1.0, scale1: Optional[float] 
     M, K = x2.shape
     out = torch.empty((M, K), dtype=x.dtype, device=x.device)
     call("mq_fakequant_act", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0),
-         float(scale0), float(scale0 if scale1 is None else scale1),
+         float(scale0), _second(scale0, scale1),
          _ptr(scale_vec0), _ptr(scale_vec1), _ptr(row_sel), int(skip_col0),
          out.data_ptr(), out.stride(0), _stream())
     return out.reshape(x.shape)
@@ -253,7 +262,7 @@ def hadamard_quant_i8(x: torch.Tensor, n: int, K: int, had_bits: Optional[torch.
     if skip_col0 and x0_out is None:
         x0_out = torch.empty((M,), dtype=torch.float32, device=x.device)
     call("mq_hadamard_quant_i8", x2.data_ptr(), dtype_code(x2.dtype), M, n_in, x2.stride(0), n, K,
-         _ptr(had_bits), _had_flags(had_bits, fp32_had, fast), float(scale0), float(scale0 if scale1 is None else scale1),
+         _ptr(had_bits), _had_flags(had_bits, fp32_had, fast), float(scale0), _second(scale0, scale1),
          _ptr(row_sel), int(skip_col0), _ptr(x0_out), optr, K_pad, ldo, _stream())
     return out, x0_out
 
@@ -291,7 +300,7 @@ def act_hadamard_quant_i8(x: torch.Tensor, x2: Optional[torch.Tensor], act: int,
     if skip_col0 and x0_out is None:
         x0_out = torch.empty((M,), dtype=torch.float32, device=x.device)
     call("mq_act_hadamard_quant_i8", a.data_ptr(), _ptr(b), int(act), dtype_code(a.dtype), M, n_in, a.stride(0),
-         n, K, _ptr(had_bits), _had_flags(had_bits, fp32_had, fast), float(scale0), float(scale0 if scale1 is None else scale1),
+         n, K, _ptr(had_bits), _had_flags(had_bits, fp32_had, fast), float(scale0), _second(scale0, scale1),
          _ptr(row_sel), int(skip_col0), _ptr(x0_out), optr, K_pad, ldo, _stream())
     return out, x0_out
 
@@ -562,7 +571,7 @@ def attn_prefill_quant_i8(q: torch.Tensor, scale0: float, scale1: Optional[float
         cp, ldc, sp = None, 0, None
     call("mq_attn_prefill_quant_i8", q.data_ptr(), dtype_code(q.dtype), T, H, hkv, D, q.stride(0) if T > 1 else H * D,
          kp, vp, ldkv, cp, ldc, sp, float(softmax_scale), 1 if causal else 0, float(scale0),
-         float(scale0 if scale1 is None else scale1), _ptr(row_sel), optr, K_pad, ldo, _stream())
+         _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo, _stream())
     return out
 
 
@@ -623,7 +632,7 @@ def gemm_w4a8(a: torch.Tensor, w_img: torch.Tensor, w_bits: int, N: int, s_x0: f
         out = torch.empty((M, N), dtype=out_dtype, device=a.device)
     ws = splitk_workspace(a.device) if use_workspace else None
     call("mq_gemm_w4a8_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad,
-         float(s_x0), float(s_x0 if s_x1 is None else s_x1), _ptr(row_sel), s_w.data_ptr(),
+         float(s_x0), _second(s_x0, s_x1), _ptr(row_sel), s_w.data_ptr(),
          _ptr(bias), _ptr(x0), _ptr(w0), out.data_ptr(), dtype_code(out.dtype), out.stride(0),
          _ptr(ws), 0 if ws is None else ws.numel(), _stream())
     return out
@@ -644,7 +653,7 @@ def gemm_w4a8_act(a, w_img: torch.Tensor, w_bits: int, N: int, s_x0: float, s_w:
         out = torch.empty((M, n_out), dtype=out_dtype, device=w_img.device)
     assert out.shape == (M, n_out)
     call("mq_gemm_w4a8_act_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, float(s_x0),
-         float(s_x0 if s_x1 is None else s_x1), _ptr(row_sel), _ptr(s_x_rows), s_w.data_ptr(), _ptr(bias), int(act),
+         _second(s_x0, s_x1), _ptr(row_sel), _ptr(s_x_rows), s_w.data_ptr(), _ptr(bias), int(act),
          out.data_ptr(), dtype_code(out.dtype), out.stride(0), _stream())
     return out
 
@@ -654,10 +663,7 @@ def quantize_act_dyn_i8(x: torch.Tensor, bits: int = 8, clip_ratio: float = 1.0,
                         out=None, tiled: bool = False):
     """Dynamic symmetric per-token quantizer (the reference's default activation mode).
     Returns (int8 [M, ceil128(K)], per-row scales fp32 [M], column 0 as fp32 [M] | None)."""
-    x2 = _rows(x)
-    _need_cuda(x2, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled)
     scale = torch.empty((M,), dtype=torch.float32, device=x.device)
     x0 = torch.empty((M,), dtype=torch.float32, device=x.device) if skip_col0 else None
     call("mq_quantize_act_dyn_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0), int(bits),
@@ -671,10 +677,7 @@ def quantize_act_group_i8(x: torch.Tensor, groupsize: int, bits: int = 8, clip_r
                           tiled: bool = False):
     """Dynamic symmetric GROUP-WISE quantizer (``--a_groupsize``; reference quant_utils.py:181-203), every
     intermediate in x's dtype like the reference.  Returns (int8 [M, ceil128(K)], scales fp32 [M, K / groupsize])."""
-    x2 = _rows(x)
-    _need_cuda(x2, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled)
     scales = torch.empty((M, K // groupsize), dtype=torch.float32, device=x.device)
     call("mq_quantize_act_group_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0), int(groupsize), int(bits),
          float(clip_ratio), scales.data_ptr(), optr, K_pad, ldo, _stream())
@@ -704,10 +707,7 @@ def quantize_act_group_asym_i8(x: torch.Tensor, groupsize: int, bits: int = 8, c
     """Dynamic ASYMMETRIC group-wise quantizer (``--a_groupsize`` + ``--a_asym``; reference quant_utils.py:181-203, sym = False),
     every intermediate in x's dtype like the reference.  Returns (stored int8 levels q - 2^(bits-1) [M, ceil128(K)], scales,
     zero points, shift = scale * (2^(bits-1) - zero): fp32 [M, K / groupsize] each)."""
-    x2 = _rows(x)
-    _need_cuda(x2, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled)
     scales, zero, shift = (torch.empty((M, K // groupsize), dtype=torch.float32, device=x.device) for _ in range(3))
     call("mq_quantize_act_group_asym_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0), int(groupsize), int(bits),
          float(clip_ratio), scales.data_ptr(), zero.data_ptr(), shift.data_ptr(), optr, K_pad, ldo, _stream())
@@ -727,7 +727,7 @@ def gemm_w4a8_rope(a, w_img: torch.Tensor, w_bits: int, N: int, s_x0: float, s_w
         out = torch.empty((M, N), dtype=out_dtype, device=s_w.device)
     assert cos.dtype == out.dtype and sin.dtype == out.dtype and cos.is_contiguous() and sin.is_contiguous()
     assert tuple(cos.shape) == tuple(sin.shape) and cos.shape[-1] == 128 and cos.numel() >= M * 128
-    call("mq_gemm_w4a8_rope_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, float(s_x0), float(s_x0 if s_x1 is None else s_x1),
+    call("mq_gemm_w4a8_rope_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, float(s_x0), _second(s_x0, s_x1),
          _ptr(row_sel), s_w.data_ptr(), _ptr(bias), cos.data_ptr(), sin.data_ptr(), int(rope_cols), 128, out.data_ptr(),
          dtype_code(out.dtype), out.stride(0), _stream())
     return out
@@ -753,7 +753,7 @@ def gemm_w4a8_wgroupscale(a, w_img: torch.Tensor, w_bits: int, N: int, s_w_group
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype, device=s_w_groups.device)
     call("mq_gemm_w4a8_wgroupscale", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, s_w_groups.data_ptr(), G, int(group_k),
-         float(s_x0), float(s_x0 if s_x1 is None else s_x1), _ptr(row_sel), _ptr(s_x_rows), _ptr(s_x_groups), _ptr(bias),
+         float(s_x0), _second(s_x0, s_x1), _ptr(row_sel), _ptr(s_x_rows), _ptr(s_x_groups), _ptr(bias),
          out.data_ptr(), dtype_code(out.dtype), out.stride(0), _stream())
     return out
 
@@ -783,10 +783,7 @@ def quantize_act_dyn_asym_i8(x: torch.Tensor, bits: int = 8, clip_ratio: float =
     """Dynamic ASYMMETRIC per-token quantizer (``--a_asym``).  Returns (stored int8 levels q - 2^(bits-1)
     [M, ceil128(K)], scale [M], zero [M], shift [M] = scale * (2^(bits-1) - zero)); dequantised value =
     scale * stored + shift."""
-    x2 = _rows(x)
-    _need_cuda(x2, out)
-    M, K = x2.shape
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled)
     scale, zero, shift = (torch.empty((M,), dtype=torch.float32, device=x.device) for _ in range(3))
     call("mq_quantize_act_dyn_asym_i8", x2.data_ptr(), dtype_code(x2.dtype), M, K, x2.stride(0), int(bits),
          float(clip_ratio), scale.data_ptr(), zero.data_ptr(), shift.data_ptr(), optr, K_pad, ldo, _stream())
@@ -799,12 +796,9 @@ def quantize_act_tensor_i8(x: torch.Tensor, bits: int = 8, clip_ratio: float = 1
     """Dynamic PER-TENSOR quantizer (``act_per_tensor``): min/max of the whole tensor on the device
     (``mq_minmax_tensor``), then ``mq_quantize_act_range_i8``.  Returns (int8 levels, scale [M], zero [M] | None,
     shift [M] | None, column 0 as fp32 [M] | None)."""
-    x2 = _rows(x)
-    _need_cuda(x2, out)
     assert not (asym and skip_col0)
-    M, K = x2.shape
+    x2, M, K, out, optr, K_pad, ldo = _quant_prologue(x, out, tiled)
     rng = minmax_tensor(x2, 1 if skip_col0 else 0)
-    out, optr, K_pad, ldo = _out_act(out, tiled, M, ceil_to(K, 128), x.device)
     scale = torch.empty((M,), dtype=torch.float32, device=x.device)
     zero = torch.empty((M,), dtype=torch.float32, device=x.device) if asym else None
     shift = torch.empty((M,), dtype=torch.float32, device=x.device) if asym else None
@@ -824,7 +818,7 @@ def act_rowsum_scaled(a, s_x0: float = 1.0, s_x1: Optional[float] = None, row_se
     aptr, lda, M, K_pad = _a_args(a)
     dev = a.data.device if isinstance(a, TiledAct) else a.device
     out = torch.empty((M,), dtype=torch.float32, device=dev)
-    call("mq_act_rowsum_scaled", aptr, lda, M, K_pad, float(s_x0), float(s_x0 if s_x1 is None else s_x1),
+    call("mq_act_rowsum_scaled", aptr, lda, M, K_pad, float(s_x0), _second(s_x0, s_x1),
          _ptr(row_sel), _ptr(s_x_rows), out.data_ptr(), _stream())
     return out
 
@@ -868,7 +862,7 @@ def gemm_w4a8_rank2(a: torch.Tensor, w_img: torch.Tensor, w_bits: int, N: int, s
         out = torch.empty((M, N), dtype=out_dtype, device=a.device)
     ws = splitk_workspace(a.device)
     call("mq_gemm_w4a8_rank2_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, float(s_x0),
-         float(s_x0 if s_x1 is None else s_x1), _ptr(row_sel), _ptr(s_x_rows), s_w.data_ptr(), _ptr(bias),
+         _second(s_x0, s_x1), _ptr(row_sel), _ptr(s_x_rows), s_w.data_ptr(), _ptr(bias),
          x0.data_ptr(), w0.data_ptr(), x1.data_ptr(), w1.data_ptr(), out.data_ptr(), dtype_code(out.dtype), out.stride(0),
          _ptr(ws), 0 if ws is None else ws.numel(), _stream())
     return out
@@ -902,7 +896,7 @@ def gemm_w4a8_residual(a: torch.Tensor, w_img: torch.Tensor, w_bits: int, N: int
     assert out.dtype == residual.dtype
     ws = splitk_workspace(a.device)
     call("mq_gemm_w4a8_residual_ws", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad,
-         float(s_x0), float(s_x0 if s_x1 is None else s_x1), _ptr(row_sel), s_w.data_ptr(), _ptr(bias), _ptr(x0),
+         float(s_x0), _second(s_x0, s_x1), _ptr(row_sel), s_w.data_ptr(), _ptr(bias), _ptr(x0),
          _ptr(w0), residual.data_ptr(), residual.stride(0), out.data_ptr(), dtype_code(out.dtype), out.stride(0),
          _ptr(ws), 0 if ws is None else ws.numel(), _stream())
     return out

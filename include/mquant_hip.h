@@ -353,8 +353,10 @@ int mq_attn_prefill_fp8kv(const void *q, int dtype, long T, int heads, int kv_he
                           int causal, void *out, long ldo, void *stream);
 /* The same kernel over UNQUANTISED K / V of q's dtype (the K and V column slices of the fused q|k|v GEMM output, read in
  * place): k / v point at the first K / V head of token 0, a token's kv_heads * head_dim values contiguous, row stride ldkv
- * ELEMENTS.  head_dim 128 or 80 (Qwen2-VL's vision tower; rows stay 16-byte aligned: 160 bytes per head).  Replaces
- * repeat_kv + scaled_dot_product_attention in the glue of the whole-prefill report. */
+ * ELEMENTS.  head_dim 128, 80 (Qwen2-VL's vision tower), 64 (InternViT-300M, InternVL2's tower) or 104 (Qwen-VL's ViT); a
+ * head stays 16-byte aligned at each (160, 128 and 208 bytes).  Nothing outside a head's own head_dim columns is read: 104 is
+ * contracted over 112 with zeros supplied inside the kernel.  Replaces repeat_kv + scaled_dot_product_attention in the glue of
+ * the whole-prefill report. */
 int mq_attn_prefill(const void *q, int dtype, long T, int heads, int kv_heads, int head_dim, long ldq,
                     const void *k, const void *v, long ldkv, float softmax_scale, int causal, void *out, long ldo,
                     void *stream);
@@ -364,8 +366,8 @@ int mq_attn_debug_waves(int waves);
 /* Either attention with the NEXT Linear's static int8 activation quantizer fused into its store (the o_proj /
  * proj input): out[t][c] = clamp(rint(cast_dtype(o[t][c]) / s_t), -128, 127), s_t = scale1 where row_sel[t] != 0 else
  * scale0 -- the bytes mq_quantize_act_i8 writes for the 16-bit attention output, in the same activation layout (K_pad ==
- * heads * head_dim, ldo = MQ_LD_TILED or a row stride).  kv_cache != NULL: the e4m3 variant (k, v, ldkv ignored); else the
- * 16-bit variant (kv_cache, ld_cache, kv_scale ignored). */
+ * heads * head_dim, a multiple of 64; ldo = MQ_LD_TILED or a row stride).  kv_cache != NULL: the e4m3 variant (k, v, ldkv
+ * ignored; head_dim 128); else the 16-bit variant (kv_cache, ld_cache, kv_scale ignored; head_dim 128, 80, 64 or 104). */
 int mq_attn_prefill_quant_i8(const void *q, int dtype, long T, int heads, int kv_heads, int head_dim, long ldq,
                              const void *k, const void *v, long ldkv, const uint8_t *kv_cache, long ld_cache,
                              const float *kv_scale, float softmax_scale, int causal, float scale0, float scale1,

@@ -2,8 +2,9 @@
 //   * mq_attn_prefill_fp8kv: consumes the fp8 (OCP e4m3fn) KV cache DIRECTLY -- K and V leave HBM as one byte per element
 //     and are widened inside the kernel; no dequantise-on-read pass, no fp16 copy of the cache in HBM (SURVEY 8(f4),
 //     BASELINE configuration 5);
-//   * mq_attn_prefill: the same dataflow over unquantised 16-bit K / V, head_dim 128 (decoder, causal) or 80 (Qwen2-VL's
-//     vision tower), q / k / v read in place from the fused q|k|v GEMM output (glue of the whole-prefill report, 8(f3));
+//   * mq_attn_prefill: the same dataflow over unquantised 16-bit K / V, head_dim 128 (decoder, causal), 80 (Qwen2-VL's
+//     vision tower), 64 (InternViT-300M, InternVL2's tower) or 104 (Qwen-VL's ViT), q / k / v read in place from the fused
+//     q|k|v GEMM output (glue of the whole-prefill report, 8(f3));
 //   * mq_attn_prefill_quant_i8: either of them with the NEXT Linear's static int8 activation quantizer fused into the store.
 // The reference has neither a KV-cache quantizer nor an attention kernel of its own (fake_quant/utils.py:220-267 are flags
 // of an unused parser; attention is HF model code): PARITY UNPINNED -- the checker is float64 softmax attention (over the
@@ -83,21 +84,37 @@ template <> struct AttnMma<MQ_BF16> {
 
 constexpr int AT_KB = 32;            // keys per block
 constexpr int AT_STATS = 4 * 32 * 2 * 4;   // [waves <= 4][32 queries][m, l]
-// Per head dimension HD (128: Qwen2-VL decoder; 80: its vision tower, 16-bit K / V only): the V tile is [32 keys][HD] 16-bit
-// values, rows padded to whole 32-column d-tiles.  HD = 128: 256-byte rows, 32-byte groups XOR-ed by key & 3; HD = 80: 192-byte
-// rows (the four rows of a transpose read already fall into four different 64-byte bank slots).  The 16-bit K tile has rows
-// of 2 HD + 16 bytes (an odd number of 16-byte slots: conflict-free ds_read_b128 with lane = key).
+// Per head dimension HD (128: Qwen2-VL decoder; 80: its vision tower; 64: InternViT; 104: Qwen-VL's ViT -- the last three with
+// 16-bit K / V only): the V tile is [32 keys][HD] 16-bit values, rows padded to whole 32-column d-tiles.  A transpose read takes
+// 64 contiguous bytes (one d-tile) of four consecutive keys per 32-lane group (bank = byte address / 4 mod 64) and is
+// conflict-free when those four pieces fall into the four different 64-byte slots of the 256-byte bank row:
+//   HD = 128: 256-byte rows, 32-byte groups XOR-ed by key & 3;
+//   HD = 80: 192-byte rows (the four rows of a transpose read already fall into four different 64-byte bank slots: 0, 3, 2, 1);
+//   HD = 104: 256-byte rows, by themselves all four keys in ONE slot -- the 64-byte d-tiles of a row are XOR-ed by key & 3:
+//            slots dt ^ 0 .. dt ^ 3, all different (and so are the 32-byte halves that one 16-lane group of the read takes);
+//   HD = 64: 128-byte rows, keys k and k + 2 share a slot (2 k + dt mod 4) -- the two 64-byte d-tiles of a row are XOR-ed
+//            by bit 1 of the key: slots dt, dt + 2, dt ^ 1, (dt ^ 1) + 2, all different, and no LDS spent on a row pad.
+// The 16-bit K tile has rows of 2 HP + 16 bytes (an odd number of 16-byte slots: conflict-free ds_read_b128 with lane = key).
+// HD = 104 is no multiple of the first GEMM's k-step: the contraction runs over HP = 112 (seven k-steps, lane half ko owns
+// d = 56 ko .. 56 ko + 55, a 112-byte offset, still 16-byte aligned) with d = 104 .. 111 ZERO ON BOTH SIDES -- the Q^T operand
+// of that k-step is never loaded and the K tile's pad columns are zeroed once before the key loop (zero on one side would not
+// do: 0 x NaN = NaN, and a neighbouring head may hold any bit pattern).  Seven k-steps against the eight of a 128-wide pad, and a
+// 240- instead of a 272-byte K row.  The second GEMM has four d-tiles; rows 104 .. 127 of the last are never stored.
 template <int HD> struct AttnGeo {
-    static constexpr int NKS = HD / 16;                       // k-steps of the first GEMM
+    static constexpr int HP = HD == 104 ? 112 : HD;           // contraction width of the first GEMM (HD, padded to k-steps)
+    static constexpr int NKS = HP / 16;                       // k-steps of the first GEMM
     static constexpr int NDT = (HD + 31) / 32;                // 32-row d-tiles of the second GEMM
-    static constexpr int HALF = HD / 2;                       // d values of one lane half
+    static constexpr int HALF = HP / 2;                       // d values of one lane half
     static constexpr int VROW = NDT * 64;                     // bytes per V row in LDS
     static constexpr int VBYTES = 32 * VROW;
-    static constexpr int KROW = 2 * HD + 16;
+    static constexpr int KROW = 2 * HP + 16;
     static constexpr int OBYTES = NDT * 16 * 64 * 4;          // a wave's partial O^T in the merge
     static constexpr int LOOP = VBYTES + 32 * KROW;
     static constexpr int WAVE_LDS = LOOP > OBYTES ? LOOP : OBYTES;
-    static __device__ __forceinline__ int vswz(int key) { return HD == 128 ? (key & 3) << 5 : 0; }
+    // V swizzle, byte offset within a row ^= (key & SWZ_MASK) << SWZ_SHIFT (the table above)
+    static constexpr int SWZ_MASK = HD == 128 || HD == 104 ? 3 : HD == 64 ? 2 : 0;
+    static constexpr int SWZ_SHIFT = HD == 104 ? 6 : 5;
+    static __device__ __forceinline__ int vswz(int key) { return (key & SWZ_MASK) << SWZ_SHIFT; }
 };
 
 template <int DT> struct AttnCvt;
@@ -131,9 +148,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
 {
     kernarg_warm<sizeof(AttnArgs), true>();                           // one scalar-load round trip for the argument block (mq_common.h)
     typedef AttnGeo<HD> G;
-    static_assert(HD == 128 || (HD == 80 && !KV8), "head dimensions built: 128, and 80 for 16-bit K / V");
+    static_assert(HD == 128 || ((HD == 80 || HD == 64 || HD == 104) && !KV8), "head dimensions built: 128, and 80 / 64 / 104 for 16-bit K / V");
     constexpr int NKS = G::NKS, NDT = G::NDT, AT_D = HD, AT_VROW = G::VROW, AT_KROW = G::KROW, AT_WAVE_LDS = G::WAVE_LDS;
-    constexpr int NR = KV8 ? 4 : (HD == 80 ? 5 : 8);                  // 16-byte loads per lane and operand and block
+    constexpr bool DENSE = !KV8 && HD != 128;                         // 16-bit rows shorter than 256 bytes: the dense loader below
+    constexpr int PPR = HD / 8, NPC = 32 * PPR;                       // 16-byte pieces of a 16-bit K / V row, of a block
+    constexpr int NR = KV8 ? 4 : (DENSE ? (NPC + 63) / 64 : 8);       // 16-byte loads per lane and operand and block
+    constexpr bool TAIL = DENSE && NPC % 64 != 0;                     // HD = 104: the last instruction has work for half the lanes
     typedef AttnMma<DT> MM;
     __shared__ __attribute__((aligned(16))) char smem[NW * AT_WAVE_LDS + AT_STATS];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -170,18 +190,20 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
     // the token-type flag of this row (fused int8 store), requested here rather than after the merge where it is used (a cold
     // byte load on the workgroup's tail; launch time unchanged within the harness's resolution -- other workgroups fill the CU)
     const unsigned sel = (p.qout && p.row_sel && q_row < p.T) ? p.row_sel[q_row] : 0;
-    const int ko = lane >> 5;                                         // lane half: d 64 ko.. of K / Q, keys + 4 ko of S, octet ko of P
+    const int ko = lane >> 5;                                         // lane half: d HALF ko.. of K / Q, keys + 4 ko of S, octet ko of P
     const float sc = (KV8 ? p.kv_scale[kvh] : 1.0f) * p.softmax_scale * 1.4426950408889634f;   // K scale and log2(e) folded into the score scale
     const float s_v = KV8 ? p.kv_scale[p.kv_heads + kvh] : 1.0f;
-    char *vt = smem + wave * AT_WAVE_LDS;                             // this wave's V tile: [32 keys][128 d] 16-bit, row-major, swizzled
+    char *vt = smem + wave * AT_WAVE_LDS;                             // this wave's V tile: [32 keys] rows of VROW bytes, 16-bit, row-major, swizzled
 
-    // ---- Q^T operand: lane = query; k-step ds covers d = 64 ko + 8 ds .. + 7 (the K operand is loaded to match) ----
+    // ---- Q^T operand: lane = query; k-step ds covers d = HALF ko + 8 ds .. + 7 (the K operand is loaded to match) ----
+    // HD = 104: the upper half's last k-step is d 104 .. 111 -- zero, NOT loaded (it is the next head's q, or, for the last head of
+    // a slice, whatever follows it)
     v4i Qf[NKS];
     {
         const unsigned short *qp = reinterpret_cast<const unsigned short *>(p.q) + q_row * p.ldq + (long)head * AT_D + G::HALF * ko;
 #pragma unroll
         for (int ds = 0; ds < NKS; ++ds)
-            Qf[ds] = (q_row < p.T) ? *reinterpret_cast<const v4i *>(qp + ds * 8) : v4i{0, 0, 0, 0};
+            Qf[ds] = (q_row < p.T && (G::HP == HD || G::HALF * ko + 8 * ds < HD)) ? *reinterpret_cast<const v4i *>(qp + ds * 8) : v4i{0, 0, 0, 0};
     }
 
     at_v16f O[NDT];
@@ -209,17 +231,20 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
     const __amdgpu_buffer_rsrc_t k_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.k) + (long)kvh * (AT_D * ESZ), 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.v) + (long)kvh * (AT_D * ESZ), 0, kv_bytes, 0x00020000);
     // HD = 80: a row is ten 16-byte pieces, a block 320 of them -- five instructions with every lane busy (instruction j, lane l:
-    // piece 64 j + l = row (64 j + l) / 10, piece (64 j + l) % 10) instead of eight with ten lanes in sixteen
+    // piece 64 j + l = row (64 j + l) / 10, piece (64 j + l) % 10) instead of eight with ten lanes in sixteen.  HD = 64: eight
+    // pieces, four instructions (row 8 j + l / 8, piece l % 8).  HD = 104: thirteen pieces, 416 a block -- seven instructions, the
+    // upper lane half of the last without work: those lanes repeat the block's last piece (in range, the line the lane below
+    // them fetches anyway) rather than run into the next key row, and what they fetched is not stored.
     const unsigned off_k = KV8 ? (unsigned)(lane & 31) * ldkv + 64 * ko : (unsigned)v_key * ldkv + pc16;
     const unsigned off_v = KV8 ? (unsigned)v_key * ldkv + v_d : off_k;
-    unsigned off80[HD == 80 ? 5 : 1];
-    int lds80[HD == 80 ? 5 : 1];                                      // row * 16 + piece of the same five pieces
-    if (HD == 80) {
+    unsigned offd[DENSE ? NR : 1];
+    int ldsd[DENSE ? NR : 1];                                         // row * 16 + piece of the same pieces
+    if (DENSE) {
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int idx = 64 * j + lane, row = idx / 10, piece = idx - 10 * row;
-            off80[j] = (unsigned)row * ldkv + 16 * piece;
-            lds80[j] = row * 16 + piece;
+        for (int j = 0; j < NR; ++j) {
+            const int idx = (TAIL && 64 * j + lane >= NPC) ? NPC - 1 : 64 * j + lane, row = idx / PPR, piece = idx - PPR * row;
+            offd[DENSE ? j : 0] = (unsigned)row * ldkv + 16 * piece;
+            ldsd[DENSE ? j : 0] = row * 16 + piece;
         }
     }
     auto load_block = [&](int kb, v4i (&kraw)[NR], v4i (&vraw)[NR]) {
@@ -227,7 +252,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             const unsigned step = KV8 ? 16 * j : 4 * j * ldkv;
-            const unsigned ok = HD == 80 ? blk + off80[HD == 80 ? j : 0] : blk + off_k + step, ov = HD == 80 ? ok : blk + off_v + step;
+            const unsigned ok = DENSE ? blk + offd[DENSE ? j : 0] : blk + off_k + step, ov = DENSE ? ok : blk + off_v + step;
             kraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(k_rs, ok, 0, 0));
             vraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(v_rs, ov, 0, 0));
         }
@@ -235,6 +260,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
 
     v4i kraw[NR], vraw[NR];
     if (wig < n_blocks) load_block(wig, kraw, vraw);
+    if (G::HP != HD) {
+        // the K tile's pad columns d = HD .. HP - 1, zeroed once: the loader never writes them, and the merge takes this
+        // wave's LDS only after the loop
+        constexpr int PADP = (G::HP - HD) / 8;
+        for (int i = lane; i < 32 * PADP; i += 64)
+            *reinterpret_cast<v4i *>(kt + (i / PADP) * AT_KROW + HD * 2 + 16 * (i % PADP)) = v4i{0, 0, 0, 0};
+    }
     const int t16 = lane & 15, g16 = (lane >> 4) & 1;
     for (int kb = wig; kb < n_blocks; kb += nwe) {
         // ---- K into MFMA operands, V into this wave's LDS tile (e4m3: widened on the way) ------------------------
@@ -250,12 +282,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
                 *reinterpret_cast<v4i *>(vt + v_key * AT_VROW + col) = a;
                 *reinterpret_cast<v4i *>(vt + v_key * AT_VROW + col + 16) = b;
             }
-        } else if (HD == 80) {
+        } else if (DENSE) {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const int r = lds80[HD == 80 ? j : 0] >> 4, pc = (lds80[HD == 80 ? j : 0] & 15) * 16;
-                *reinterpret_cast<v4i *>(kt + r * AT_KROW + pc) = kraw[j % NR];
-                *reinterpret_cast<v4i *>(vt + r * AT_VROW + pc) = vraw[j % NR];
+            for (int j = 0; j < NR; ++j) {
+                const int r = ldsd[DENSE ? j : 0] >> 4, pc = (ldsd[DENSE ? j : 0] & 15) * 16;
+                if (!TAIL || j < NR - 1 || 64 * j + lane < NPC) {
+                    *reinterpret_cast<v4i *>(kt + r * AT_KROW + pc) = kraw[j];
+                    *reinterpret_cast<v4i *>(vt + r * AT_VROW + (pc ^ G::vswz(r))) = vraw[j];
+                }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -337,8 +371,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
                 // A operand: row d = 32 dt + (lane & 31), keys 16 ks + 8 ko + 0..7, two transpose reads of [4 k][16 d]
-                // (HD = 80: rows 80..95 of the last tile hold whatever the padding holds; an output row depends on its own
-                //  operand row only, and those rows are never stored)
+                // (HD = 80 / 104: rows 80..95 / 104..127 of the last tile hold whatever the padding holds; an output row
+                //  depends on its own operand row only, and those rows are never stored)
                 const int d_lane = dt * 32 + 16 * g16 + 4 * (t16 & 3);
                 const int kA = ks * 16 + 8 * ko + (t16 >> 2);
                 const at_v4s r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
@@ -386,7 +420,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
 #pragma unroll
     for (int dt0 = 0; dt0 < NDT; dt0 += NWE) {
         const int dt = dt0 + wig;                                    // wave-uniform
-        if (dt >= NDT) break;                                         // HD = 80: three d-tiles
+        if (dt >= NDT) break;                                         // HD = 80: three d-tiles, HD = 64: two
         float acc[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
@@ -407,7 +441,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_prefill_kernel(AttnArgs p)
             quant_levels_i8_packed<16>(v16, qs, qinv, qrcp, w4);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if (dt * 32 + 8 * g >= HD) break;                     // HD = 80: the last tile holds d 64 .. 79 only
+                if (dt * 32 + 8 * g >= HD) break;                     // HD = 80 / 104: the last tile holds d 64 .. 79 / 96 .. 103 only
                 const long col = (long)head * AT_D + dt * 32 + 8 * g + 4 * ko;
                 *reinterpret_cast<unsigned *>(p.qout + act_offset(q_row, col, p.q_kpad, p.q_ld)) = w4[g];
             }
@@ -446,6 +480,9 @@ static void attn_launch_t(mq::AttnArgs a, int dtype, hipStream_t st)
     // 0.75 n rows) take that form: 7B shape 672 -> 504 workgroups, 18.2 (unpaired) / 17.3 (2 waves) -> 16.2 us, e4m3 18.6 / 16.1 ->
     // 15.6; a grid that fits anyway is better left alone (512 tokens: 11.6 -> 13.5 paired), a larger one goes to 2 waves (72B: 28.8
     // against 32.3 paired).
+    // head_dim 64 and 104 (vision towers, non-causal) keep the 4-wave form, as 80 does, on these timings: InternViT (1025 tokens,
+    // 16 heads of 64: 528 workgroups, past 512 like the grids that take 2 waves at 128) 16.4 us with 4 waves against 17.8 with 2;
+    // Qwen-VL's ViT (1024 tokens, 16 heads of 104: 512 workgroups) 22.9 against 25.3 us.
     const long rows_paired = n / 2 + (n - n / 2 + 1) / 2;
     const bool fits = a.heads * n <= 512, fits_paired = a.causal && n >= 2 && a.heads * rows_paired <= 512;
     int nw = (HD == 128 && !fits && !fits_paired) ? 2 : 4;
@@ -479,7 +516,9 @@ static int attn_launch(const mq::AttnArgs &a, int dtype, bool kv8, int head_dim,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (kv8) attn_launch_t<128, true>(a, dtype, st);
     else if (head_dim == 128) attn_launch_t<128, false>(a, dtype, st);
-    else attn_launch_t<80, false>(a, dtype, st);
+    else if (head_dim == 80) attn_launch_t<80, false>(a, dtype, st);
+    else if (head_dim == 64) attn_launch_t<64, false>(a, dtype, st);
+    else attn_launch_t<104, false>(a, dtype, st);
     return mq::check_launch("attn_prefill");
 }
 
@@ -513,7 +552,7 @@ extern "C" int mq_attn_prefill(const void *q, int dtype, long T, int heads, int 
     using namespace mq;
     MQ_REQUIRE(dtype == MQ_F16 || dtype == MQ_BF16, "mq_attn_prefill: dtype must be fp16 or bf16 (got %d)", dtype);
     MQ_REQUIRE(T >= 0 && heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0, "mq_attn_prefill: bad head counts %d / %d", heads, kv_heads);
-    MQ_REQUIRE(head_dim == 128 || head_dim == 80, "mq_attn_prefill: head_dim %d (built: 128 and 80)", head_dim);
+    MQ_REQUIRE(head_dim == 128 || head_dim == 80 || head_dim == 64 || head_dim == 104, "mq_attn_prefill: head_dim %d (built: 128, 80, 64 and 104)", head_dim);
     MQ_REQUIRE(softmax_scale > 0.0f && softmax_scale < 3.0e38f, "mq_attn_prefill: softmax_scale must be positive and finite (got %g)", (double)softmax_scale);
     if (T == 0) return MQ_OK;
     MQ_REQUIRE(q && k && v && out, "mq_attn_prefill: null pointer");
@@ -536,7 +575,8 @@ extern "C" int mq_attn_prefill_quant_i8(const void *q, int dtype, long T, int he
     MQ_REQUIRE(dtype == MQ_F16 || dtype == MQ_BF16, "mq_attn_prefill_quant_i8: dtype must be fp16 or bf16 (got %d)", dtype);
     MQ_REQUIRE(T >= 0 && heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0, "mq_attn_prefill_quant_i8: bad head counts %d / %d", heads, kv_heads);
     const bool kv8 = kv_cache != nullptr;
-    MQ_REQUIRE(head_dim == 128 || (head_dim == 80 && !kv8), "mq_attn_prefill_quant_i8: head_dim %d (built: 128, and 80 for 16-bit K / V)", head_dim);
+    MQ_REQUIRE(head_dim == 128 || ((head_dim == 80 || head_dim == 64 || head_dim == 104) && !kv8),
+               "mq_attn_prefill_quant_i8: head_dim %d (built: 128, and 80, 64 and 104 for 16-bit K / V)", head_dim);
     MQ_REQUIRE(softmax_scale > 0.0f && softmax_scale < 3.0e38f, "mq_attn_prefill_quant_i8: softmax_scale must be positive and finite (got %g)", (double)softmax_scale);
     if (T == 0) return MQ_OK;
     const long D = head_dim;

@@ -78,7 +78,7 @@ class FullPrefill:
         #: (mq_attn_prefill_quant_i8) instead of a 16-bit tensor plus a quantize launch
         self.attn_quant = own
         self.attn_kernel = own and self.g.head_dim == 128
-        self.vis_attn_kernel = own and self.g.vis_dim // self.g.vis_heads in (80, 128)      # the vision tower's (non-causal) attention
+        self.vis_attn_kernel = own and self.g.vis_dim // self.g.vis_heads in (64, 80, 104, 128)      # the vision tower's (non-causal) attention
         #: the decoder's RoPE rides in the q|k|v GEMM's store (mq_gemm_w4a8_rope_ws) instead of its own launch (round 5)
         self.rope_fused = fused_glue
         #: silu(gate) * up and the vision tower's QuickGELU ride in the store of the PRODUCING GEMM (mq_gemm_w4a8_act_ws, round 6):

@@ -505,7 +505,8 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool
                  out: torch.Tensor = None) -> torch.Tensor:
     """Prefill attention over unquantised K / V (``mq_attn_prefill``): q [T, heads, D], k and v [T, kv_heads, D] of the
     same fp16 / bf16 dtype and the same token stride (column slices of the fused q|k|v output work in place), D = 128
-    (Qwen2-VL decoder) or 80 (its vision tower) -> [T, heads * D], the layout o_proj / proj consumes."""
+    (the decoders), 80 (Qwen2-VL's vision tower), 64 (InternViT-300M, InternVL2's tower) or 104 (Qwen-VL's ViT)
+    -> [T, heads * D], the layout o_proj / proj consumes.  Any other D is refused (``MQuantHipError``)."""
     _need_cuda(q, k, v, out)
     T, H, D = q.shape
     assert k.shape == v.shape and k.shape[0] == T and k.shape[2] == D and k.dtype == q.dtype and v.dtype == q.dtype
@@ -549,7 +550,8 @@ def attn_prefill_quant_i8(q: torch.Tensor, scale0: float, scale1: Optional[float
                           out=None, tiled: bool = False):
     """``attn_prefill`` (k, v) or ``attn_prefill_fp8kv`` (kv_cache, kv_scale) with the next Linear's static int8 quantizer
     fused into the store (``mq_attn_prefill_quant_i8``): returns the int8 activations ``quantize_act_i8`` would produce
-    from the 16-bit attention output ([T, heads * D] row-major, or a ``TiledAct``)."""
+    from the 16-bit attention output ([T, heads * D] row-major, or a ``TiledAct``).  k / v: D = 128, 80, 64 or 104;
+    kv_cache: D = 128; heads * D must be a multiple of 64 (the activation layout's column group)."""
     _need_cuda(q, k, v, kv_cache, kv_scale, row_sel, out)
     T, H, D = q.shape
     assert q.stride(2) == 1 and q.stride(1) == D

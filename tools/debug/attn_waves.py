@@ -26,6 +26,7 @@ def timed(fn, iters=30):
     return ts[len(ts) // 2]
 
 for name, T, H, HKV, D, causal in (("7B decoder", 768, 28, 4, 128, True), ("72B decoder", 768, 64, 8, 128, True), ("vision tower", 1024, 16, 16, 80, False),
+                                   ("InternViT-300M", 1025, 16, 16, 64, False), ("Qwen-VL ViT", 1024, 16, 16, 104, False),
                                    ("7B, 512 tokens", 512, 28, 4, 128, True), ("7B, 1536 tokens", 1536, 28, 4, 128, True), ("7B, 4096 tokens", 4096, 28, 4, 128, True)):
     qkv = torch.randn(T, (H + 2 * HKV) * D, device=dev).half()
     q = qkv[:, :H * D].view(T, H, D); k = qkv[:, H * D:(H + HKV) * D].view(T, HKV, D); v = qkv[:, (H + HKV) * D:].view(T, HKV, D)

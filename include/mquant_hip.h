@@ -373,6 +373,50 @@ int mq_attn_prefill_quant_i8(const void *q, int dtype, long T, int heads, int kv
                              const float *kv_scale, float softmax_scale, int causal, float scale0, float scale1,
                              const uint8_t *row_sel, int8_t *out, long K_pad, long ldo, void *stream);
 
+/* Decode attention straight off the e4m3 cache: the generation-step counterpart of mq_attn_prefill_fp8kv (the same arithmetic, no
+ * reference counterpart, parity unpinned; checker = softmax attention over the dequantised cache, tests/attn_decode_reference.py).
+ * R query rows (1 .. 8, the LAST R positions of a sequence of n tokens) attend over the first n keys of a cache of capacity >= T:
+ *     O[r][h][:] = softmax_k((Q[r][h] . K8[k][g]) * s[g] * softmax_scale) @ V8[k][g] * s[kv_heads + g],  g = h / (heads / kv_heads)
+ * causal != 0: row r attends keys 0 .. n - R + r (R == 1: all n keys); causal == 0: every row attends all n keys.
+ * n_keys_dev == NULL: n = T.  Else n = clamp(*n_keys_dev, R, T), read on the device by the launches themselves, and T is only the
+ * capacity the plan and the grid are sized for: a generation loop is captured once and replayed while the cache grows.  Nothing at
+ * or beyond key n reaches the output, whatever those cache rows hold.
+ * q / out: [R][ld] elements of `dtype` (MQ_F16 / MQ_BF16) with heads * head_dim values per row (ldq lets the Q columns of a fused
+ * q|k|v GEMM output be read in place); kv_cache: [T][ldkv] bytes, per token the K heads then the V heads (the layout
+ * mq_kv_quant_fp8 writes for the K|V columns); kv_scale: [2 * kv_heads] floats.  head_dim == 128; q / cache rows 16-byte aligned,
+ * out rows 8-byte aligned.
+ * One workgroup serves one (kv head, range of keys): a cache byte is fetched once per kv head, not once per query head; R * heads /
+ * kv_heads <= 16 is one pass over the keys, more rows take several.  When the plan cuts the keys into more than one range, every
+ * range writes a partial state into `workspace` (fp32, 16-byte aligned, at least mq_attn_decode_workspace_bytes(R, T, heads,
+ * kv_heads) bytes) and a second launch on the same stream merges the ranges in index order: same inputs, same plan, same bits.
+ * The workspace needs no initialisation and holds nothing between calls. */
+int mq_attn_decode_fp8kv(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
+                         long ldq, const uint8_t *kv_cache, long ldkv, const float *kv_scale, float softmax_scale, int causal,
+                         void *out, long ldo, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the NEXT Linear's static int8 activation quantizer fused into the final store, exactly as
+ * mq_attn_prefill_quant_i8 defines it: out[r][c] = clamp(rint(cast_dtype(o[r][c]) / s_r), -128, 127), s_r = scale1 where
+ * row_sel[r] != 0 else scale0 (K_pad == heads * head_dim, a multiple of 64; ldo = MQ_LD_TILED or a row stride). */
+int mq_attn_decode_fp8kv_quant_i8(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
+                                  long ldq, const uint8_t *kv_cache, long ldkv, const float *kv_scale, float softmax_scale, int causal,
+                                  float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of workspace the plan of such a call needs: 0 when the keys are not split.  Host arithmetic only (0 also for arguments the
+ * call would refuse). */
+size_t mq_attn_decode_workspace_bytes(int R, long T, int heads, int kv_heads);
+/* TEST-ONLY, thread-local: force the number of key ranges and / or the keys per range (a multiple of 32) of the decode attention;
+ * 0 = the heuristic.  A forced pair that does not cut T keys into non-empty ranges is refused by the call. */
+int mq_attn_decode_debug_force(int splits, int keys_per_split);
+/* TEST-ONLY: what the host decides for a call with these arguments and the calling thread's mq_attn_decode_debug_force setting --
+ * the launch is driven by the same function.  Host arithmetic only (without a device the CU count is taken as 256).  plan receives
+ * MQ_ATTN_DECODE_PLAN_INTS ints.  Returns the code (and mq_last_error the message) of the call for arguments the call refuses. */
+#define MQ_ATTN_DECODE_PLAN_SPLITS 0           /* key ranges */
+#define MQ_ATTN_DECODE_PLAN_KEYS_PER_SPLIT 1   /* keys per range, a multiple of the 32-key block */
+#define MQ_ATTN_DECODE_PLAN_GRID 2             /* workgroups of the first launch: kv_heads x splits */
+#define MQ_ATTN_DECODE_PLAN_PASSES 3           /* passes over the keys inside a workgroup: ceil(R * heads / kv_heads / 16) */
+#define MQ_ATTN_DECODE_PLAN_WORKSPACE 4        /* workspace bytes */
+#define MQ_ATTN_DECODE_PLAN_INTS 5
+int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads, int *plan);
+
 /* out[m][n] = sum_k x[m][k] * W[n][k], 16-bit x ([M <= 8, K], ldx elements per row) and W ([N, K], ldw), fp32 products and sums,
  * one rounding to the same 16-bit dtype: the UNQUANTIZED lm_head on the last position(s) of a prefill (the reference leaves
  * lm_head in 16 bits: exam/quant_qwen2vl.py:130-143 wraps the decoder's and the vision tower's Linears only; HF computes

@@ -36,16 +36,10 @@
 // lane); the grid is (heads, rows of query tiles) with the deepest tiles of every head first, the second round of a causal launch
 // reversed, and -- where that brings a causal grid into one round of slots -- the shallow half of the tiles paired two to a
 // workgroup; launches beyond one round take 2-wave workgroups (attn_launch_t).
-#include "mq_common.h"
+#include "attn_common.h"
 #include <type_traits>
 
 namespace mq {
-
-typedef short at_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) at_v4s at_lds_v4s;
-typedef _Float16 at_v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 at_v8bf __attribute__((ext_vector_type(8)));
-typedef float at_v16f __attribute__((ext_vector_type(16)));
 
 struct AttnArgs {
     const void *q;           // [T, heads * 128] (row stride ldq elements), fp16 / bf16
@@ -66,20 +60,6 @@ struct AttnArgs {
     int deep_rows;           // grid rows that are ONE query tile (the deepest ones); the rows after them carry two (see the kernel)
     float qi0, qi1;          // 1 / qs0, 1 / qs1 (IEEE, from the host) and whether the reciprocal form may be used (quant_rcp_ok)
     int qr0, qr1;
-};
-
-template <int DT> struct AttnMma;
-template <> struct AttnMma<MQ_F16> {
-    static __device__ __forceinline__ at_v16f mma(v4i a, v4i b, at_v16f c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(at_v8h, a), __builtin_bit_cast(at_v8h, b), c, 0, 0, 0);
-    }
-};
-template <> struct AttnMma<MQ_BF16> {
-    static __device__ __forceinline__ at_v16f mma(v4i a, v4i b, at_v16f c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(at_v8bf, a), __builtin_bit_cast(at_v8bf, b), c, 0, 0, 0);
-    }
 };
 
 constexpr int AT_KB = 32;            // keys per block
@@ -116,29 +96,6 @@ template <int HD> struct AttnGeo {
     static constexpr int SWZ_SHIFT = HD == 104 ? 6 : 5;
     static __device__ __forceinline__ int vswz(int key) { return (key & SWZ_MASK) << SWZ_SHIFT; }
 };
-
-template <int DT> struct AttnCvt;
-typedef float at_v2f __attribute__((ext_vector_type(2)));
-template <> struct AttnCvt<MQ_F16> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(at_v2f{a, b}, h2)); }   // V_CVT_PK_F16_F32, RNE
-    static __device__ __forceinline__ int lo(int w) { return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)); }
-    static __device__ __forceinline__ int hi(int w) { return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true)); }
-};
-template <> struct AttnCvt<MQ_BF16> {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(at_v2f{a, b}, b2)); }   // V_CVT_PK_BF16_F32, RNE
-    static __device__ __forceinline__ int lo(int w) { return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false)); }
-    static __device__ __forceinline__ int hi(int w) { return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true)); }
-};
-
-// sixteen e4m3 bytes -> two operands of eight 16-bit values (exact: e4m3 has 3 mantissa bits)
-template <int DT>
-__device__ __forceinline__ void widen16(const v4i w, v4i &a, v4i &b)
-{
-    a = v4i{AttnCvt<DT>::lo(w[0]), AttnCvt<DT>::hi(w[0]), AttnCvt<DT>::lo(w[1]), AttnCvt<DT>::hi(w[1])};
-    b = v4i{AttnCvt<DT>::lo(w[2]), AttnCvt<DT>::hi(w[2]), AttnCvt<DT>::lo(w[3]), AttnCvt<DT>::hi(w[3])};
-}
 
 // KV8: K / V are e4m3 bytes (widened here); else they are 16-bit values of q's dtype, used as they are.
 // NW = waves per workgroup = ways the keys are split (4, or 2: half the LDS, so four workgroups fit a CU and a prefill whose

@@ -577,6 +577,105 @@ def attn_prefill_quant_i8(q: torch.Tensor, scale0: float, scale1: Optional[float
     return out
 
 
+_DECODE_WS = {}
+_DECODE_PINNED = []      # outgrown decode workspaces that a captured hipGraph may still replay into (as _SPLITK_PINNED)
+
+
+def attn_decode_workspace_bytes(R: int, T: int, heads: int, kv_heads: int) -> int:
+    """Bytes of workspace the plan of a decode attention call needs (``mq_attn_decode_workspace_bytes``): 0 when the keys are not
+    split.  Host arithmetic only."""
+    return int(_lib.load().mq_attn_decode_workspace_bytes(R, T, heads, kv_heads))
+
+
+def attn_decode_debug_force(splits: int = 0, keys_per_split: int = 0) -> None:
+    """Test hook: force the key ranges / keys per range of the decode attention (0 = the heuristic)."""
+    call("mq_attn_decode_debug_force", splits, keys_per_split)
+
+
+def attn_decode_plan(R: int, T: int, heads: int, kv_heads: int) -> dict:
+    """What the host decides for a decode attention call (``mq_attn_decode_debug_plan``); raises for arguments the call refuses."""
+    import ctypes
+    plan = (ctypes.c_int * 5)()
+    call("mq_attn_decode_debug_plan", R, T, heads, kv_heads, ctypes.cast(plan, ctypes.c_void_p))
+    return dict(zip(("splits", "keys_per_split", "grid", "passes", "workspace_bytes"), plan))
+
+
+def _decode_workspace(device, nbytes: int) -> torch.Tensor:
+    """Per-device scratch for the partial states of the key ranges: ONE grow-only buffer per device, reused by every call in the
+    device's current stream order.  A buffer handed out during stream capture is kept alive when a larger one replaces it."""
+    key = (device.index or 0)
+    ent = _DECODE_WS.get(key)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if ent is None or ent[0].numel() < nbytes:
+        if ent is not None and ent[1]:
+            _DECODE_PINNED.append(ent[0])
+        ent = [torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=device), False]
+        _DECODE_WS[key] = ent
+    ent[1] = ent[1] or capturing
+    return ent[0]
+
+
+def _decode_args(q, kv_cache, kv_scale, n_keys, workspace):
+    """The arguments the two decode entry points share: (R, T, n_keys_dev, heads, kv_heads, ldq, ldkv, workspace ptr, bytes)."""
+    R, H, D = q.shape
+    cap, H2, D2 = kv_cache.shape
+    assert D2 == D and H2 % 2 == 0 and kv_cache.dtype == torch.float8_e4m3fn
+    assert q.stride(2) == 1 and q.stride(1) == D and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
+    hkv = H2 // 2
+    _check_kv_scale(kv_scale, hkv)
+    if isinstance(n_keys, torch.Tensor):
+        assert n_keys.dtype == torch.int32 and n_keys.numel() == 1 and n_keys.is_cuda, "n_keys: an int or an int32 CUDA tensor of one element"
+        T, n_dev = cap, n_keys.data_ptr()
+    else:
+        T, n_dev = (cap if n_keys is None else int(n_keys)), None
+        assert T <= cap, f"n_keys = {T} exceeds the cache's capacity {cap}"
+    need = attn_decode_workspace_bytes(R, T, H, hkv)
+    if workspace is None and need:
+        workspace = _decode_workspace(q.device, need)
+    wptr, wbytes = (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
+    return (R, T, n_dev, H, hkv, D, q.stride(0) if R > 1 else H * D, kv_cache.stride(0) if cap > 1 else H2 * D, wptr, wbytes)
+
+
+@_on_device
+def attn_decode_fp8kv(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.Tensor, n_keys=None, causal: bool = True,
+                      softmax_scale: float = None, out: torch.Tensor = None, workspace: torch.Tensor = None) -> torch.Tensor:
+    """Decode attention that reads the e4m3 cache directly (``mq_attn_decode_fp8kv``): q [R, heads, 128] fp16 / bf16, the
+    LAST R <= 8 positions of the sequence (may be a column slice of the fused q|k|v output), kv_cache [capacity, 2 * kv_heads, 128]
+    float8_e4m3fn (K heads then V heads, what ``kv_quant_fp8`` writes for the K|V columns), kv_scale [2 * kv_heads]
+    -> [R, heads * 128].  n_keys: how many cache rows hold keys -- an int (default: the capacity) or an int32 CUDA tensor of one
+    element, read on the device by the kernel (a captured generation step then replays while the cache grows).  causal: row r
+    attends keys 0 .. n - R + r.  workspace: a buffer of at least ``attn_decode_workspace_bytes`` bytes instead of the wrapper's."""
+    _need_cuda(q, kv_cache, kv_scale, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
+    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace)
+    if out is None:
+        out = torch.empty((R, H * D), dtype=q.dtype, device=q.device)
+    assert out.dtype == q.dtype and out.shape == (R, H * D) and out.stride(1) == 1
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    call("mq_attn_decode_fp8kv", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
+         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, out.data_ptr(), out.stride(0) if R > 1 else H * D,
+         wptr, wbytes, _stream())
+    return out
+
+
+@_on_device
+def attn_decode_quant_i8(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.Tensor, scale0: float,
+                         scale1: Optional[float] = None, *, n_keys=None, causal: bool = True, softmax_scale: float = None,
+                         row_sel: Optional[torch.Tensor] = None, out=None, tiled: bool = False, workspace: torch.Tensor = None):
+    """``attn_decode_fp8kv`` with the next Linear's static int8 quantizer fused into the final store
+    (``mq_attn_decode_fp8kv_quant_i8``): returns the int8 activations ``quantize_act_i8`` would produce from the 16-bit decode
+    output of the same plan ([R, heads * 128] row-major, or a ``TiledAct``)."""
+    _need_cuda(q, kv_cache, kv_scale, row_sel, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
+    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace)
+    out, optr, K_pad, ldo = _out_act(out, tiled, R, H * D, q.device)
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    call("mq_attn_decode_fp8kv_quant_i8", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
+         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel),
+         optr, K_pad, ldo, wptr, wbytes, _stream())
+    return out
+
+
 def kv_scale_from_absmax(kv: torch.Tensor) -> torch.Tensor:
     """Static per-head scale from calibration activations [T, kv_heads, head_dim]: absmax / 448."""
     return (kv.float().abs().amax(dim=(0, 2)).clamp_min(1e-8) / FP8_E4M3_MAX).contiguous()

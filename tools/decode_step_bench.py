@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One decoder layer's hot path at generation shapes (M rows): the four quantize(+Hadamard) launches and the four W4A8 GEMMs of a Qwen2-VL-7B
 layer (q|k|v, o_proj, gate|up, down_proj with its online Hadamard over 19968 padded channels), replayed from one hipGraph over 8 copies of
-the weights (cold weights).  usage (GPU box): python3 tools/decode_step_bench.py"""
+the weights (cold weights), and -- a line of its own, M <= 8 -- what sits between q|k|v and o_proj: the cache append and the decode
+attention over the e4m3 cache.  usage (GPU box): python3 tools/decode_step_bench.py"""
 import os
 import sys
 
@@ -14,6 +15,7 @@ from mquant_amd import ops  # noqa: E402
 
 dev = torch.device("cuda:0")
 G = 8
+N_KEYS = 4096     # keys in the cache at the timed step
 
 
 def graph_time(fn, reps=20):
@@ -43,6 +45,8 @@ def main():
     s_w = {k: torch.full((n,), 0.01, device=dev) for k, (n, _) in shapes.items()}
     _, K = hu.get_hadK(19968)
     bits = hu.had_sign_bits(K, dev)
+    kv_scale = torch.full((8,), 0.01, device=dev)
+    caches = [torch.randn((N_KEYS, 8, 128), device=dev).mul_(100).clamp_(-448, 448).to(torch.float8_e4m3fn) for _ in range(G)]
     for M in (1, 4, 16, 64):
         x = torch.randn((M, 3584), device=dev, dtype=torch.float16)
         xd = torch.randn((M, 18944), device=dev, dtype=torch.float16)
@@ -72,6 +76,19 @@ def main():
         tq, tg, tl = graph_time(quant_only) / G, graph_time(gemm_only) / G, graph_time(layer) / G
         print(f"M={M:3d}: quantizers + Hadamard {tq:6.1f} us | GEMMs {tg:6.1f} us | layer (8 launches + reduces) {tl:6.1f} us "
               f"-> {28 * tl / 1e3:5.2f} ms per token-step of 28 layers (weights alone at 6.3 TB/s: 0.53 ms)", flush=True)
+        if M <= 8:
+            # what sits between q|k|v and o_proj: the cache append (the step's K|V rows quantized into place) and the decode attention of the
+            # M newest positions over the e4m3 cache, one cache per weight copy
+            def attention():
+                for g in range(G):
+                    ops.kv_quant_fp8(kv_new, kv_scale, out=caches[g][N_KEYS - M:N_KEYS])
+                    ops.attn_decode_fp8kv(q_new, caches[g], kv_scale, out=attn_out)
+            kv_new = outs["qkv"][:, 3584:].view(M, 8, 128)
+            q_new = outs["qkv"][:, :3584].view(M, 28, 128)
+            attn_out = torch.empty((M, 3584), dtype=torch.float16, device=dev)
+            ta = graph_time(attention) / G
+            print(f"M={M:3d}: cache append + decode attention over {N_KEYS} keys (e4m3 cache, 28 / 4 heads) {ta:6.1f} us "
+                  f"-> {28 * ta / 1e3:5.2f} ms per token-step of 28 layers", flush=True)
 
 
 if __name__ == "__main__":

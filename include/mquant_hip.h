@@ -417,6 +417,28 @@ int mq_attn_decode_debug_force(int splits, int keys_per_split);
 #define MQ_ATTN_DECODE_PLAN_INTS 5
 int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads, int *plan);
 
+/* The launch in front of mq_attn_decode_fp8kv in a generation step: rotate Q and K of the R new rows (1 .. 8) in place and
+ * quantise K|V into rows [n - R, n) of the e4m3 cache, at a position read from DEVICE memory -- with it a whole decode step is
+ * captured once and advances by incrementing one int32 (no reference counterpart; checkers = mq_rope_inplace and mq_kv_quant_fp8).
+ * qkv: [R][ldqkv] elements of `dtype` (MQ_F16 / MQ_BF16), the fused projection output: per row `heads` Q heads, kv_heads K heads,
+ * kv_heads V heads, head_dim wide each.  n = n_keys_dev ? clamp(*n_keys_dev, R, T) : T is the key count AFTER the append -- the
+ * integer and the clamp of mq_attn_decode_fp8kv, which runs next on the stream; T = capacity of the cache in rows.  Row r is token
+ * t = n - R + r and takes row p = clamp(t + (rope_delta_dev ? *rope_delta_dev : 0), 0, table_rows - 1) of the tables (cos / sin:
+ * [table_rows][head_dim] in `dtype`, contiguous; the offset is HF Qwen2-VL's rope_deltas: after an image the text position is not
+ * the cache index).  Both clamps are memory safety, not semantics: no device value moves an access outside the buffers the host
+ * checked.
+ *   - the Q and K columns of qkv receive the bits of mq_rope_inplace(row r, heads + kv_heads, head_dim, cos + p * head_dim, sin + ..);
+ *   - cache row t receives the rotated K heads, then the V heads: the bytes of mq_kv_quant_fp8 applied to the rotated row
+ *     (kv_scale: [2 * kv_heads] floats), in the layout the attention kernels read;
+ *   - the V columns of qkv and every other cache byte (padding between 2 * kv_heads * head_dim and ldkv included) are not written.
+ * cos == NULL && sin == NULL: append only, nothing is rotated; exactly one of them NULL is refused.  head_dim a multiple of 16;
+ * qkv rows and the tables 16-byte aligned, cache rows 8-byte aligned, the device integers 4-byte aligned.  One launch whose grid
+ * depends on R, heads, kv_heads and head_dim only. */
+int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                          int heads, int kv_heads, int head_dim, long ldqkv,
+                          const void *cos, const void *sin, long table_rows,
+                          uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream);
+
 /* out[m][n] = sum_k x[m][k] * W[n][k], 16-bit x ([M <= 8, K], ldx elements per row) and W ([N, K], ldw), fp32 products and sums,
  * one rounding to the same 16-bit dtype: the UNQUANTIZED lm_head on the last position(s) of a prefill (the reference leaves
  * lm_head in 16 bits: exam/quant_qwen2vl.py:130-143 wraps the decoder's and the vision tower's Linears only; HF computes

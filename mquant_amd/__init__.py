@@ -1,6 +1,7 @@
 """MI355X-native W4A8 static-quant kernels behind MQuant's ``fake_quant`` operator API.
 
 ``mquant_amd.ops``   torch-tensor front-end of the C ABI (``include/mquant_hip.h``)
+``mquant_amd.kv_cache``  ``Fp8KVCache``: the e4m3 cache of a captured generation step (its length lives on the device)
 ``mquant_amd._lib``  ctypes loader of ``libmquant_hip.so`` (no CPU fallback)
 ``mquant_amd.csrc``  the hand-written gfx950 kernels
 """

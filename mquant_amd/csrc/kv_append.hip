@@ -1,0 +1,152 @@
+// kv_append.hip -- the launch between the fused q|k|v projection and the decode attention of a generation step: rotate Q and K
+// of the R new rows in place (rotate-half RoPE) and quantise K|V into rows [n - R, n) of the e4m3 cache, with n -- and an
+// optional RoPE position offset -- read from DEVICE memory.  One launch where mq_rope_inplace and mq_kv_quant_fp8 were two, and
+// neither of those can be captured once for a growing cache: both take their position from the host (a pointer into the tables,
+// a pointer into the cache).  With this one a whole decode step is a linear graph that advances by incrementing one int32:
+//
+//     n = n_keys_dev ? clamp(*n_keys_dev, R, T) : T          the key count AFTER the append: what mq_attn_decode_fp8kv reads next
+//     t = n - R + r                                          token (= cache row) of row r
+//     p = clamp(t + (rope_delta_dev ? *rope_delta_dev : 0), 0, table_rows - 1)      row of the cos / sin tables
+//
+// The clamps are MEMORY SAFETY, not semantics: the host checks the buffers against R, T and table_rows, and whatever the two
+// device integers hold, every access stays inside those buffers.  A caller that lets n leave [R, T] or p leave the tables gets
+// a defined, wrong-position result instead of a fault.
+//
+// No reference counterpart (the reference neither rotates nor quantises a cache): the checkers are this library's own
+// mq_rope_inplace and mq_kv_quant_fp8, bit for bit -- the arithmetic is theirs (kv_rope_common.h): the rotated value is
+// rounded to the dtype, and that rounded value is what is divided by the head's scale.
+//
+// Element-wise and tiny (the 7B geometry at R = 8: 8 x 36 x 128 elements, nine workgroups): the cost is one dispatch, so the
+// argument block is pulled in one round trip and the two device integers arrive through the vector memory path (a buffer load
+// every lane of which receives the same dword), as in attn_decode.hip.  One lane = eight rotate-half pairs of a Q or K head
+// (two 16-byte loads and stores; a K lane also stores two 8-byte groups of e4m3) or sixteen elements of a V head (two 16-byte
+// loads, two 8-byte stores).  The grid depends on R, heads, kv_heads and head_dim only -- never on n.
+#include "kv_rope_common.h"
+
+namespace mq {
+
+struct KvAppendArgs {
+    void *qkv;                 // [R][ldqkv]: per row `heads` Q heads, kv_heads K heads, kv_heads V heads
+    const void *cos, *sin;     // [table_rows][head_dim], or both null: append only
+    uint8_t *kv;               // e4m3 cache: [T][ldkv] bytes, per token the K heads, then the V heads
+    const float *kv_scale;     // [2 * kv_heads]
+    const int32_t *n_dev;      // optional device-side key count (after the append)
+    const int32_t *delta_dev;  // optional device-side RoPE position offset
+    long T, ldqkv, ldkv, table_rows;
+    int R, heads, kv_heads, head_dim;
+};
+
+// one int32 through the VECTOR memory path (see decode_key_count in attn_decode.hip)
+__device__ __forceinline__ int load_device_int(const int32_t *ptr)
+{
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(ptr), 0, 4, 0x00020000);
+    return __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0));
+}
+
+template <int DT>
+__device__ __forceinline__ v2i append_quant8(const v8us &x, float s)
+{
+    typedef typename Elem<DT>::T E;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = Elem<DT>::ld((E)x[e]);
+    return kv_quant8_e4m3(v, s);
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
+{
+    kernarg_warm<sizeof(KvAppendArgs)>();
+    typedef typename Elem<DT>::T E;
+    long n = p.T, delta = 0;
+    if (p.n_dev) {
+        n = load_device_int(p.n_dev);
+        n = n < p.R ? p.R : n;                                       // memory safety: rows [n - R, n) lie inside [0, T)
+        n = n > p.T ? p.T : n;
+    }
+    if (p.delta_dev) delta = load_device_int(p.delta_dev);
+
+    const unsigned gph = (unsigned)p.head_dim / 16;                   // lanes per head
+    const unsigned per_row = (unsigned)(p.heads + 2 * p.kv_heads) * gph;
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= (unsigned)p.R * per_row) return;
+    const unsigned r = i / per_row, j = i - r * per_row;
+    const unsigned hh = j / gph, g = j - hh * gph;                    // head of the row (Q, K, V in this order), lane of the head
+    const long t = n - p.R + r;
+    const int D = p.head_dim, half = D / 2, qk = p.heads + p.kv_heads;
+    E *row = reinterpret_cast<E *>(p.qkv) + (long)r * p.ldqkv;
+    uint8_t *crow = p.kv + t * p.ldkv;
+
+    if ((int)hh >= qk) {                                              // ---- V: sixteen consecutive elements, quantised as they are
+        const int vh = p.kv_heads + ((int)hh - qk);                   // head of the cache row
+        const E *src = row + (long)hh * D + g * 16;
+        const v8us x0 = *reinterpret_cast<const v8us *>(src), x1 = *reinterpret_cast<const v8us *>(src + 8);
+        const float s = p.kv_scale[vh];
+        uint8_t *dst = crow + (long)vh * D + g * 16;
+        *reinterpret_cast<v2i *>(dst) = append_quant8<DT>(x0, s);
+        *reinterpret_cast<v2i *>(dst + 8) = append_quant8<DT>(x1, s);
+        return;
+    }
+    const bool rotate = p.cos != nullptr;
+    if ((int)hh < p.heads && !rotate) return;                         // append only: Q stays as it is
+    E *x = row + (long)hh * D + g * 8;
+    v8us a8 = *reinterpret_cast<const v8us *>(x), b8 = *reinterpret_cast<const v8us *>(x + half);
+    if (rotate) {
+        long pos = t + delta;                                         // memory safety: the table row lies inside [0, table_rows)
+        pos = pos < 0 ? 0 : pos;
+        pos = pos > p.table_rows - 1 ? p.table_rows - 1 : pos;
+        const E *ct = reinterpret_cast<const E *>(p.cos) + pos * D + g * 8, *st = reinterpret_cast<const E *>(p.sin) + pos * D + g * 8;
+        const v8us c0 = *reinterpret_cast<const v8us *>(ct), c1 = *reinterpret_cast<const v8us *>(ct + half);
+        const v8us s0 = *reinterpret_cast<const v8us *>(st), s1 = *reinterpret_cast<const v8us *>(st + half);
+        v8us lo8, hi8;
+        rope_pairs8<DT>(a8, b8, c0, c1, s0, s1, lo8, hi8);
+        *reinterpret_cast<v8us *>(x) = lo8;
+        *reinterpret_cast<v8us *>(x + half) = hi8;
+        a8 = lo8;                                                     // the cache receives the ROUNDED rotated values
+        b8 = hi8;
+    }
+    if ((int)hh >= p.heads) {                                         // ---- K: the two halves of the rotated head
+        const int kh = (int)hh - p.heads;
+        const float s = p.kv_scale[kh];
+        uint8_t *dst = crow + (long)kh * D + g * 8;
+        *reinterpret_cast<v2i *>(dst) = append_quant8<DT>(a8, s);
+        *reinterpret_cast<v2i *>(dst + half) = append_quant8<DT>(b8, s);
+    }
+}
+
+}  // namespace mq
+
+extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                                     int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
+                                     uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream)
+{
+    using namespace mq;
+    const char *who = "mq_kv_append_rope_fp8";
+    MQ_REQUIRE(qkv && kv_cache && kv_scale, "%s: null pointer", who);
+    MQ_REQUIRE(dtype == MQ_F16 || dtype == MQ_BF16, "%s: qkv dtype must be fp16 or bf16 (got %d)", who, dtype);
+    MQ_REQUIRE(R >= 1 && R <= 8, "%s: R = %d new rows (1 .. 8)", who, R);
+    MQ_REQUIRE(T >= R, "%s: T = %ld cache rows for R = %d new rows (the rows are the last R positions: T >= R)", who, T, R);
+    MQ_REQUIRE(heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0, "%s: bad head counts %d / %d", who, heads, kv_heads);
+    MQ_REQUIRE(head_dim >= 16 && head_dim % 16 == 0, "%s: head_dim %d (a multiple of 16)", who, head_dim);
+    const long cols = ((long)heads + 2L * kv_heads) * head_dim;
+    MQ_REQUIRE(cols < (1L << 31) / 8, "%s: %ld columns per row exceed the grid", who, cols);
+    MQ_REQUIRE(ldqkv >= cols, "%s: qkv row stride %ld shorter than (heads + 2 kv_heads) * head_dim = %ld", who, ldqkv, cols);
+    MQ_REQUIRE(((uintptr_t)qkv) % 16 == 0 && (ldqkv * 2) % 16 == 0, "%s: qkv rows must be 16-byte aligned", who);
+    MQ_REQUIRE(ldkv >= 2L * kv_heads * head_dim, "%s: cache row stride %ld shorter than 2 kv_heads * head_dim = %ld", who, ldkv, 2L * kv_heads * head_dim);
+    MQ_REQUIRE(((uintptr_t)kv_cache) % 8 == 0 && ldkv % 8 == 0, "%s: cache rows must be 8-byte aligned", who);
+    MQ_REQUIRE((cos == nullptr) == (sin == nullptr), "%s: cos and sin must both be given or both be null (append only)", who);
+    if (cos) {
+        MQ_REQUIRE(table_rows >= 1, "%s: table_rows = %ld (at least one row of cos / sin)", who, table_rows);
+        MQ_REQUIRE(((uintptr_t)cos) % 16 == 0 && ((uintptr_t)sin) % 16 == 0, "%s: cos / sin tables must be 16-byte aligned", who);
+    }
+    MQ_REQUIRE(((uintptr_t)n_keys_dev) % 4 == 0, "%s: n_keys_dev must be 4-byte aligned", who);
+    MQ_REQUIRE(((uintptr_t)rope_delta_dev) % 4 == 0, "%s: rope_delta_dev must be 4-byte aligned", who);
+
+    KvAppendArgs a{qkv, cos, sin, kv_cache, kv_scale, n_keys_dev, rope_delta_dev, T, ldqkv, ldkv, table_rows, R, heads, kv_heads, head_dim};
+    const unsigned lanes = (unsigned)(R * (cols / 16));
+    const dim3 grid((lanes + 255) / 256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MQ_F16) hipLaunchKernelGGL(kv_append_rope_kernel<MQ_F16>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(kv_append_rope_kernel<MQ_BF16>, grid, dim3(256), 0, st, a);
+    return check_launch("kv_append_rope_fp8");
+}

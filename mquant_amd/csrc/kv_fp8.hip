@@ -8,7 +8,7 @@
 // gfx950 converts with V_CVT_PK_FP8_F32 / V_CVT_F32_FP8 (OCP encoding on CDNA4, round-to-nearest-
 // even); the clamp in front makes the result independent of the conversion's overflow mode.
 // HBM-bound: 2 (or 4) bytes in, 1 byte out per element; 8 elements per lane per access.
-#include "mq_common.h"
+#include "kv_rope_common.h"
 
 namespace mq {
 
@@ -42,18 +42,9 @@ __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(KvArgs p)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = Elem<DT>::ld(h[e]);
         }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float q = v[e] / s;
-            q = fminf(fmaxf(q, -448.0f), 448.0f);
-            v[e] = q;
-        }
-        int w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-        *reinterpret_cast<v2i *>(reinterpret_cast<uint8_t *>(p.dst) + t * p.ldd + c) = v2i{w0, w1};
+        const v2i w = kv_quant8_e4m3(v, s);
+        const int w0 = w[0], w1 = w[1];
+        *reinterpret_cast<v2i *>(reinterpret_cast<uint8_t *>(p.dst) + t * p.ldd + c) = w;
         if (p.hat) {
             // what a later read of the cache returns (kv_dequant_fp8_kernel), handed to the attention of THIS step
             // in the same launch: prefill and decode then attend over identical K / V, and the dequantise-on-read

@@ -4,7 +4,7 @@
 // model's glue and the torch composition of RoPE costs ~8 launches per layer.  Semantics = the HF
 // formula on tensors of dtype DT, one rounding per torch op:
 //     out = cast(cast(x * cos) + cast(rotate_half(x) * sin)),  rotate_half(x) = cat(-x2, x1)
-#include "mq_common.h"
+#include "kv_rope_common.h"
 
 namespace mq {
 
@@ -26,8 +26,8 @@ __global__ __launch_bounds__(256) void rope_kernel(void *x_, long T, int heads, 
         const float a = Elem<DT>::ld(p[d]), b = Elem<DT>::ld(p[d + half]);
         const float c0 = Elem<DT>::ld(cs[t * head_dim + d]), c1 = Elem<DT>::ld(cs[t * head_dim + d + half]);
         const float s0 = Elem<DT>::ld(sn[t * head_dim + d]), s1 = Elem<DT>::ld(sn[t * head_dim + d + half]);
-        const float lo = Elem<DT>::rnd(a * c0) + Elem<DT>::rnd(-b * s0);
-        const float hi = Elem<DT>::rnd(b * c1) + Elem<DT>::rnd(a * s1);
+        float lo, hi;
+        rope_pair<DT>(a, b, c0, c1, s0, s1, lo, hi);
         p[d] = Elem<DT>::st(lo);
         p[d + half] = Elem<DT>::st(hi);
     }
@@ -54,14 +54,7 @@ __global__ __launch_bounds__(256) void rope_vec_kernel(void *x_, unsigned groups
     const v8us c0 = *reinterpret_cast<const v8us *>(ct), c1 = *reinterpret_cast<const v8us *>(ct + half);
     const v8us s0 = *reinterpret_cast<const v8us *>(st), s1 = *reinterpret_cast<const v8us *>(st + half);
     v8us lo8, hi8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float a = Elem<DT>::ld((E)a8[e]), b = Elem<DT>::ld((E)b8[e]);
-        const float lo = Elem<DT>::rnd(a * Elem<DT>::ld((E)c0[e])) + Elem<DT>::rnd(-b * Elem<DT>::ld((E)s0[e]));
-        const float hi = Elem<DT>::rnd(b * Elem<DT>::ld((E)c1[e])) + Elem<DT>::rnd(a * Elem<DT>::ld((E)s1[e]));
-        lo8[e] = (unsigned short)Elem<DT>::st(lo);
-        hi8[e] = (unsigned short)Elem<DT>::st(hi);
-    }
+    rope_pairs8<DT>(a8, b8, c0, c1, s0, s1, lo8, hi8);
     *reinterpret_cast<v8us *>(p) = lo8;
     *reinterpret_cast<v8us *>(p + half) = hi8;
 }

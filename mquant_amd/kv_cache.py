@@ -1,0 +1,86 @@
+"""An e4m3 KV cache whose length lives on the device: the state a captured generation step needs.
+
+Per layer one cache ``[capacity, 2 * kv_heads, head_dim]`` (K heads then V heads, what ``ops.kv_quant_fp8`` writes), and for all
+layers ONE int32 ``n_keys`` on the device -- the number of cache rows that hold keys -- plus an optional int32 ``rope_delta``
+(HF Qwen2-VL's ``rope_deltas``: after an image the text position is not the cache index).  A generation step is
+
+    cache.advance(R)                       # n_keys += R, on the device, once per step
+    for every layer:  qkv = <q|k|v projection of the R new rows>;  o = cache.step(layer, qkv, heads, out=...)
+
+where ``step`` is two native calls that both read ``n_keys`` themselves: ``ops.kv_append_rope_fp8`` (rotate Q and K, quantise K|V
+into rows [n - R, n)) and ``ops.attn_decode_fp8kv``.  The class keeps NO host copy of the length: after one warm-up step (the
+decode workspace and the one-time check of the scales happen there) ``advance`` and ``step`` with ``out`` given neither
+synchronise nor allocate, so the step is captured once into a graph and replayed while the cache grows."""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from . import ops
+
+
+class Fp8KVCache:
+    def __init__(self, layers: int, capacity: int, kv_heads: int, head_dim: int, kv_scales: Sequence[torch.Tensor],
+                 cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], device, dtype: torch.dtype,
+                 rope_delta: Optional[int] = None):
+        """kv_scales: per layer a float32 [2 * kv_heads] tensor (K scales then V scales; a [layers, 2 * kv_heads] tensor works).
+        cos / sin: the RoPE tables [rows, head_dim] in ``dtype`` (contiguous), or both None for a model without rotation at this
+        point.  rope_delta: the initial position offset; None = no offset tensor at all (``set_rope_delta`` makes one later)."""
+        device = torch.device(device)
+        assert len(kv_scales) == layers and (cos is None) == (sin is None)
+        self.layers, self.capacity, self.kv_heads, self.head_dim, self.dtype = layers, capacity, kv_heads, head_dim, dtype
+        self.scales = [s.to(device=device, dtype=torch.float32).contiguous() for s in kv_scales]
+        for s in self.scales:
+            assert s.numel() == 2 * kv_heads
+        if cos is not None:
+            assert cos.shape == sin.shape and cos.dim() == 2 and cos.shape[1] == head_dim
+            cos, sin = cos.to(device=device, dtype=dtype).contiguous(), sin.to(device=device, dtype=dtype).contiguous()
+        self.cos, self.sin = cos, sin
+        self.caches = [torch.zeros((capacity, 2 * kv_heads, head_dim), dtype=torch.uint8, device=device).view(torch.float8_e4m3fn)
+                       for _ in range(layers)]
+        self.n_keys = torch.zeros((1,), dtype=torch.int32, device=device)
+        self.rope_delta = None
+        if rope_delta is not None:
+            self.set_rope_delta(rope_delta)
+
+    # ---- host side: prefill and bookkeeping (not for a captured step) ----
+    def fill(self, layer: int, kv_cols: torch.Tensor) -> torch.Tensor:
+        """The prefill write: kv_cols [T, 2 * kv_heads, head_dim] (K already rotated; the K|V columns of the fused q|k|v output work
+        in place) into rows [0, T) of the layer's cache.  The length is set by ``set_length``, once for all layers."""
+        T = kv_cols.shape[0]
+        assert T <= self.capacity and tuple(kv_cols.shape[1:]) == (2 * self.kv_heads, self.head_dim)
+        return ops.kv_quant_fp8(kv_cols, self.scales[layer], out=self.caches[layer][:T])
+
+    def set_length(self, n: int) -> None:
+        assert 0 <= n <= self.capacity, f"length {n} outside the capacity {self.capacity}"
+        self.n_keys.fill_(int(n))
+
+    def set_rope_delta(self, delta: int) -> None:
+        """Set the position offset from the host.  The tensor is made on the first call: make it before a step is captured."""
+        if self.rope_delta is None:
+            self.rope_delta = torch.zeros((1,), dtype=torch.int32, device=self.n_keys.device)
+        self.rope_delta.fill_(int(delta))
+
+    # ---- the generation step: capturable ----
+    def advance(self, R: int = 1) -> None:
+        """n_keys += R on the device: once per step, before the layers."""
+        self.n_keys.add_(int(R))
+
+    def _append(self, layer: int, qkv: torch.Tensor, heads: int) -> torch.Tensor:
+        ops.kv_append_rope_fp8(qkv, heads, self.caches[layer], self.scales[layer], self.cos, self.sin, n_keys=self.n_keys,
+                               rope_delta=self.rope_delta)
+        return qkv[:, :heads * self.head_dim].view(qkv.shape[0], heads, self.head_dim)
+
+    def step(self, layer: int, qkv: torch.Tensor, heads: int, causal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """qkv [R, (heads + 2 * kv_heads) * head_dim], the raw projection of the R newest positions (``advance(R)`` came first):
+        rotated and appended in place, then attended over the first n_keys rows -> [R, heads * head_dim]."""
+        q = self._append(layer, qkv, heads)
+        return ops.attn_decode_fp8kv(q, self.caches[layer], self.scales[layer], n_keys=self.n_keys, causal=causal, out=out)
+
+    def step_quant_i8(self, layer: int, qkv: torch.Tensor, heads: int, scale0: float, scale1: Optional[float] = None, *,
+                      causal: bool = True, row_sel: Optional[torch.Tensor] = None, out=None, tiled: bool = False):
+        """``step`` with the next Linear's static int8 quantizer fused into the attention's store (``ops.attn_decode_quant_i8``)."""
+        q = self._append(layer, qkv, heads)
+        return ops.attn_decode_quant_i8(q, self.caches[layer], self.scales[layer], scale0, scale1, n_keys=self.n_keys, causal=causal,
+                                        row_sel=row_sel, out=out, tiled=tiled)

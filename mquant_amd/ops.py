@@ -676,6 +676,55 @@ def attn_decode_quant_i8(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torc
     return out
 
 
+def _device_int(v, name: str, device) -> Optional[torch.Tensor]:
+    """A device-side integer argument: an int32 CUDA tensor of one element as it is, a Python int as a fresh one (a fill on the current
+    stream: keep a tensor of your own for a step that must not allocate), None as None."""
+    if v is None or isinstance(v, torch.Tensor):
+        assert v is None or (v.dtype == torch.int32 and v.numel() == 1 and v.is_cuda), f"{name}: an int or an int32 CUDA tensor of one element"
+        return v
+    return torch.full((1,), int(v), dtype=torch.int32, device=device)
+
+
+@_on_device
+def kv_append_rope_fp8(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv_scale: torch.Tensor, cos: torch.Tensor = None,
+                       sin: torch.Tensor = None, n_keys=None, rope_delta=None) -> torch.Tensor:
+    """The launch between the fused q|k|v projection and the decode attention of a generation step (``mq_kv_append_rope_fp8``): qkv
+    [R <= 8, (heads + 2 * kv_heads) * D] fp16 / bf16 (a strided view works) has its Q and K columns rotated in place -- the bits of
+    ``rope_inplace`` -- and its rotated K | V columns quantised into rows [n - R, n) of kv_cache [capacity, 2 * kv_heads, D]
+    float8_e4m3fn -- the bytes of ``kv_quant_fp8``.  n_keys: the key count AFTER the append, what ``attn_decode_fp8kv`` takes next --
+    an int (default: the capacity) or an int32 CUDA tensor of one element, read on the device (clamped to [R, capacity]).  Row r is
+    token t = n - R + r and uses row clamp(t + rope_delta, 0, rows - 1) of cos / sin [rows, D] (qkv's dtype, contiguous);
+    rope_delta: an int or an int32 CUDA tensor of one element (HF Qwen2-VL's ``rope_deltas``), default 0.  cos = sin = None: append
+    only.  With both integers on the device a captured step replays while the cache grows.  Returns qkv."""
+    is_t = lambda v: v if isinstance(v, torch.Tensor) else None
+    _need_cuda(qkv, kv_cache, kv_scale, cos, sin, is_t(n_keys), is_t(rope_delta))
+    cap, H2, D = kv_cache.shape
+    assert H2 % 2 == 0 and kv_cache.dtype == torch.float8_e4m3fn and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
+    hkv = H2 // 2
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (heads + H2) * D, \
+        f"qkv must be [R, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}] (got {tuple(qkv.shape)})"
+    R = qkv.shape[0]
+    _check_kv_scale(kv_scale, hkv)
+    if isinstance(n_keys, torch.Tensor):
+        T, n_dev = cap, _device_int(n_keys, "n_keys", qkv.device)
+    else:
+        T, n_dev = (cap if n_keys is None else int(n_keys)), None
+        assert T <= cap, f"n_keys = {T} exceeds the cache's capacity {cap}"
+    assert (cos is None) == (sin is None), "cos and sin: both or neither"
+    rows = 0
+    if cos is not None:
+        assert cos.dtype == qkv.dtype == sin.dtype and cos.dim() == 2 and cos.shape[1] == D and cos.shape == sin.shape
+        assert cos.is_contiguous() and sin.is_contiguous()
+        rows = cos.shape[0]
+    if cos is None or (not isinstance(rope_delta, torch.Tensor) and not rope_delta):
+        rope_delta = None                                              # no table, or a host-side 0: nothing to offset
+    d_dev = _device_int(rope_delta, "rope_delta", qkv.device)
+    call("mq_kv_append_rope_fp8", qkv.data_ptr(), dtype_code(qkv.dtype), R, T, _ptr(n_dev), _ptr(d_dev), heads, hkv, D,
+         qkv.stride(0) if R > 1 else qkv.shape[1], _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(),
+         kv_cache.stride(0) if cap > 1 else H2 * D, kv_scale.data_ptr(), _stream())
+    return qkv
+
+
 def kv_scale_from_absmax(kv: torch.Tensor) -> torch.Tensor:
     """Static per-head scale from calibration activations [T, kv_heads, head_dim]: absmax / 448."""
     return (kv.float().abs().amax(dim=(0, 2)).clamp_min(1e-8) / FP8_E4M3_MAX).contiguous()

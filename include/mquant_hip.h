@@ -446,6 +446,33 @@ int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_
  * streamed once at the chip's HBM rate.  K a multiple of 8, rows 16-byte aligned, M * K * 2 bytes <= 64 KiB. */
 int mq_gemv_f16(const void *x, int dtype, int M, long K, long ldx, const void *w, long N, long ldw, void *out, long ldo,
                 void *stream);
+/* The same product with the greedy token picked on the device: the last launch of a captured generation step.  y[m][n] are the
+ * 16-bit values mq_gemv_f16 stores for the same arguments, bit for bit (one kernel template, the same grid, row hand-out and
+ * summation order).  logits != NULL: those bits are written there exactly as mq_gemv_f16 writes them ([M][ldo], ldo >= N);
+ * logits == NULL: no logit reaches memory at all.  token_out[m] (device, int32) = argmax over n of the ROUNDED y[m][n] by IEEE
+ * comparison, as the CPU torch.argmax defines it: among equal values the lowest index, -0 equals +0, a NaN counts as maximal and the
+ * first NaN wins.  Every workgroup of the first launch writes M partial (value, index) results, 8 bytes each, into `workspace`
+ * (16-byte aligned, at least mq_gemv_argmax_workspace_bytes(M, N) bytes); a second launch on the same stream takes their maximum
+ * -- associative and commutative, so no atomics and no arrival counter: same inputs, same token.  The workspace needs no
+ * initialisation and holds nothing between calls.  Everything mq_gemv_f16 requires, and 1 <= N < 2^31 (an argmax over nothing is
+ * refused); token_out 4-byte aligned.  M == 0 returns MQ_OK and writes nothing. */
+int mq_gemv_f16_argmax(const void *x, int dtype, int M, long K, long ldx, const void *w, long N, long ldw, void *logits, long ldo,
+                       int32_t *token_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of workspace such a call needs: workgroups of the launch plan x M x 8, rounded up to 16.  Host arithmetic only (without a
+ * device the CU count is taken as 256); 0 for arguments the call refuses (and for M == 0, which needs none). */
+size_t mq_gemv_argmax_workspace_bytes(int M, long N);
+
+/* The first launch of a captured generation step: out[r][0 .. dim) = table[clamp(ids_dev[r], 0, vocab - 1)][0 .. dim), a bit copy of
+ * R = 1 .. 8 rows of a 16-bit embedding table ([vocab][ldt] elements of `dtype`, MQ_F16 / MQ_BF16) at ids read from DEVICE memory --
+ * what mq_gemv_f16_argmax left in token_out -- so a step feeds itself (no reference counterpart; checker = the rows themselves).
+ * id_log != NULL: the clamped id of row r is also stored at id_log[n - R + r], n = n_keys_dev ? clamp(*n_keys_dev, R, log_rows) :
+ * log_rows -- the integer and the clamp of mq_kv_append_rope_fp8, so the log ([log_rows] int32) is indexed by cache position and the
+ * host reads N generated ids after N replays.  Both clamps are memory safety, not semantics: no device value moves an access outside
+ * the buffers the host checked.  Nothing else is written: no other log entry, no byte of out beyond dim in a row.  dim a multiple
+ * of 8, table and out rows 16-byte aligned (16-byte loads and stores), the device integers 4-byte aligned.  One launch whose grid
+ * depends on R and dim only. */
+int mq_embed_gather(const void *table, int dtype, long vocab, long dim, long ldt, const int32_t *ids_dev, int R, void *out, long ldo,
+                    int32_t *id_log, long log_rows, const int32_t *n_keys_dev, void *stream);
 
 
 /* ---------------------------------------------------------------------------

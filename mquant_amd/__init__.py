@@ -2,7 +2,18 @@
 
 ``mquant_amd.ops``   torch-tensor front-end of the C ABI (``include/mquant_hip.h``)
 ``mquant_amd.kv_cache``  ``Fp8KVCache``: the e4m3 cache of a captured generation step (its length lives on the device)
+``mquant_amd.generate``  ``GreedyLoop``: embed -> layers -> norm -> lm_head -> token as one graph that feeds itself (the token lives there too)
 ``mquant_amd._lib``  ctypes loader of ``libmquant_hip.so`` (no CPU fallback)
 ``mquant_amd.csrc``  the hand-written gfx950 kernels
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):      # the two classes of a captured generation step, imported on first use (they pull in torch)
+    if name == "Fp8KVCache":
+        from .kv_cache import Fp8KVCache
+        return Fp8KVCache
+    if name == "GreedyLoop":
+        from .generate import GreedyLoop
+        return GreedyLoop
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -36,13 +36,6 @@ struct KvAppendArgs {
     int R, heads, kv_heads, head_dim;
 };
 
-// one int32 through the VECTOR memory path (see decode_key_count in attn_decode.hip)
-__device__ __forceinline__ int load_device_int(const int32_t *ptr)
-{
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(ptr), 0, 4, 0x00020000);
-    return __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0));
-}
-
 template <int DT>
 __device__ __forceinline__ v2i append_quant8(const v8us &x, float s)
 {

@@ -125,6 +125,14 @@ __device__ __forceinline__ void kernarg_warm()
 #endif
 }
 
+// One int32 that the HOST does not know (a key count, a token id) through the VECTOR memory path: a buffer load every lane of
+// which receives the same dword (see decode_key_count in attn_decode.hip), made wave-uniform for the address arithmetic behind it.
+__device__ __forceinline__ int load_device_int(const int32_t *ptr)
+{
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(ptr), 0, 4, 0x00020000);
+    return __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0));
+}
+
 template <int DT> struct Elem;
 template <> struct Elem<MQ_F16> {
     typedef unsigned short T;

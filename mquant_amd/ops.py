@@ -543,6 +543,64 @@ def gemv_f16(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None) -> torc
     return out
 
 
+def gemv_argmax_workspace_bytes(M: int, N: int) -> int:
+    """Bytes of workspace a ``gemv_f16_argmax`` call needs (``mq_gemv_argmax_workspace_bytes``): 0 for arguments the call refuses.
+    Host arithmetic only."""
+    return int(_lib.load().mq_gemv_argmax_workspace_bytes(M, N))
+
+
+@_on_device
+def gemv_f16_argmax(x: torch.Tensor, w: torch.Tensor, *, logits: torch.Tensor = None, token_out: torch.Tensor = None,
+                    workspace: torch.Tensor = None) -> torch.Tensor:
+    """``gemv_f16`` with the greedy token picked on the device (``mq_gemv_f16_argmax``): returns int32 [M], the argmax over n of the
+    16-bit values ``gemv_f16(x, w)`` holds -- ``torch.argmax`` of the CPU: lowest index among equals, -0 == +0, the first NaN wins.
+    logits: an [M, N] buffer that receives exactly what ``gemv_f16`` writes; None: no logits are written anywhere.  token_out: an
+    int32 [M] CUDA tensor to write into (a captured generation step keeps ONE and feeds ``embed_gather`` from it); with it given,
+    and after one warm-up call, the op neither allocates nor synchronises.  workspace: a buffer of at least
+    ``gemv_argmax_workspace_bytes(M, N)`` bytes instead of the wrapper's."""
+    _need_cuda(x, w, logits, token_out, workspace)
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and w.dtype == x.dtype and x.stride(1) == 1 and w.stride(1) == 1
+    if logits is not None:
+        assert logits.dtype == x.dtype and logits.shape == (M, N) and logits.stride(1) == 1
+    if token_out is None:
+        token_out = torch.empty((M,), dtype=torch.int32, device=x.device)
+    assert token_out.dtype == torch.int32 and token_out.shape == (M,) and token_out.is_contiguous()
+    if workspace is None:
+        workspace = _decode_workspace(x.device, gemv_argmax_workspace_bytes(M, N))      # scratch in stream order, like the attention's
+    call("mq_gemv_f16_argmax", x.data_ptr(), dtype_code(x.dtype), M, K, x.stride(0) if M > 1 else K, w.data_ptr(), N,
+         w.stride(0) if N > 1 else K, _ptr(logits), (logits.stride(0) if M > 1 else N) if logits is not None else 0,
+         token_out.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream())
+    return token_out
+
+
+@_on_device
+def embed_gather(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = None, id_log: torch.Tensor = None,
+                 n_keys: torch.Tensor = None) -> torch.Tensor:
+    """Rows of a 16-bit embedding table at ids read on the device (``mq_embed_gather``): table [vocab, dim] fp16 / bf16 (dim a
+    multiple of 8), ids int32 [R <= 8] on the device -- what ``gemv_f16_argmax`` left in ``token_out`` -- -> [R, dim], bit copies of
+    rows clamp(id, 0, vocab - 1).  id_log: an int32 [log_rows] CUDA tensor that also receives the clamped id of row r at
+    [n - R + r], n = clamp(n_keys, R, log_rows) for an int32 CUDA tensor of one element (``Fp8KVCache.n_keys`` AFTER ``advance``: the
+    log is indexed by cache position), n = log_rows for None."""
+    _need_cuda(table, ids, out, id_log, n_keys)
+    vocab, dim = table.shape
+    assert table.stride(1) == 1 and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
+    R = ids.shape[0]
+    if out is None:
+        out = torch.empty((R, dim), dtype=table.dtype, device=table.device)
+    assert out.dtype == table.dtype and out.shape == (R, dim) and out.stride(1) == 1
+    log_rows = 0
+    if id_log is not None:
+        assert id_log.dtype == torch.int32 and id_log.dim() == 1 and id_log.is_contiguous()
+        log_rows = id_log.shape[0]
+    assert n_keys is None or (isinstance(n_keys, torch.Tensor) and n_keys.dtype == torch.int32 and n_keys.numel() == 1), \
+        "n_keys: an int32 CUDA tensor of one element or None"
+    call("mq_embed_gather", table.data_ptr(), dtype_code(table.dtype), vocab, dim, table.stride(0) if vocab > 1 else dim,
+         ids.data_ptr(), R, out.data_ptr(), out.stride(0) if R > 1 else dim, _ptr(id_log), log_rows, _ptr(n_keys), _stream())
+    return out
+
+
 @_on_device
 def attn_prefill_quant_i8(q: torch.Tensor, scale0: float, scale1: Optional[float] = None, *, k: torch.Tensor = None,
                           v: torch.Tensor = None, kv_cache: torch.Tensor = None, kv_scale: torch.Tensor = None,
@@ -601,8 +659,9 @@ def attn_decode_plan(R: int, T: int, heads: int, kv_heads: int) -> dict:
 
 
 def _decode_workspace(device, nbytes: int) -> torch.Tensor:
-    """Per-device scratch for the partial states of the key ranges: ONE grow-only buffer per device, reused by every call in the
-    device's current stream order.  A buffer handed out during stream capture is kept alive when a larger one replaces it."""
+    """Per-device scratch for the partial states of the key ranges (and the partial maxima of ``gemv_f16_argmax``): ONE grow-only buffer
+    per device, reused by every call in the device's current stream order.  A buffer handed out during stream capture is kept alive
+    when a larger one replaces it."""
     key = (device.index or 0)
     ent = _DECODE_WS.get(key)
     capturing = torch.cuda.is_current_stream_capturing()

@@ -97,3 +97,36 @@ def test_rope_inplace_equals_the_torch_formula(dtype, T, heads, kvh, d):
     assert torch.equal(qkv[:, :heads * d].view(T, heads, d), want_q)
     assert torch.equal(qkv[:, heads * d:(heads + kvh) * d].view(T, kvh, d), want_k)
     assert torch.equal(qkv[:, (heads + kvh) * d:], v_before)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("placement", ["one-element-in", "stride-not-a-multiple-of-8"])
+def test_rope_inplace_scalar_kernel_on_16_bit_rows(dtype, placement):
+    """16-bit rows that fail the vector kernel's alignment test take the scalar kernel -- the checker of the cache-append and the
+    fused RoPE GEMM tests.  1100 x 16 x 64 = 1.13 M pairs are more than its 4096 workgroups of 256 hold: the grid-stride loop runs.
+    Bits of ``_rope``; V, the element in front of the first row and the elements behind every row keep theirs."""
+    from mquant_amd import ops
+    from mquant_amd.full_prefill import _rope, _rope_tables
+    T, heads, kvh, d = 1100, 14, 2, 128
+    qk, cols = (heads + kvh) * d, (heads + 2 * kvh) * d
+    assert T * (heads + kvh) * (d // 2) > 4096 * 256
+    lead, ld = (1, cols + 8) if placement == "one-element-in" else (0, cols + 4)
+    vals = torch.from_numpy(make_x(3, (T, cols))).to(device=DEV, dtype=dtype)
+    flat = torch.full((lead + T * ld,), 7.0, dtype=dtype, device=DEV)
+    rows = flat[lead:].view(T, ld)
+    rows[:, :cols] = vals
+    x = rows[:, :qk]
+    assert x.data_ptr() % 16 != 0 or (x.stride(0) * 2) % 16 != 0      # the vector kernel's test fails
+    cos, sin = _rope_tables(T, d, torch.device(DEV), dtype)
+    want = torch.full_like(flat, 7.0)
+    want_rows = want[lead:].view(T, ld)
+    want_rows[:, :heads * d] = _rope(vals[:, :heads * d].view(T, heads, d), cos, sin).reshape(T, -1)
+    want_rows[:, heads * d:qk] = _rope(vals[:, heads * d:qk].view(T, kvh, d), cos, sin).reshape(T, -1)
+    want_rows[:, qk:cols] = vals[:, qk:]
+    ops.rope_inplace(x, heads + kvh, d, cos[:, 0].contiguous(), sin[:, 0].contiguous())
+    got_rows = flat[lead:].view(T, ld)
+    assert torch.equal(got_rows[:, :qk].view(torch.int16), want_rows[:, :qk].view(torch.int16))            # rotated q | k
+    assert not torch.equal(got_rows[1:, :qk], vals[1:, :qk])
+    assert torch.equal(got_rows[:, qk:cols].view(torch.int16), vals[:, qk:].view(torch.int16))             # V
+    assert bool((got_rows[:, cols:] == 7.0).all()) and (lead == 0 or float(flat[0]) == 7.0)
+    assert torch.equal(flat.view(torch.int16), want.view(torch.int16))                                     # the whole buffer

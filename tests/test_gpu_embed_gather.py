@@ -12,6 +12,9 @@ torch.set_grad_enabled(False)
 DTYPES = [torch.float16, torch.bfloat16]
 DT_IDS = ["fp16", "bf16"]
 TABLES = [(1001, 1288), (37, 8)]            # (vocab, dim): 161 chunks of 16 bytes (one workgroup, partly idle) and a single chunk
+# rows wider than one workgroup's 256 chunks (dim > 2048): 2056 = 257 chunks, the second workgroup has ONE live lane; 3584 (the 7B
+# model dim) = 448, the second is partly idle; 4096 = exactly two full workgroups; 8200 = 1025, five workgroups, the last with one lane
+WIDE_DIMS = [2056, 3584, 4096, 8200]
 LOG_ROWS = 40
 POISON_ID = -77
 
@@ -64,6 +67,20 @@ def test_rows_are_bit_copies(dtype, vocab, dim, R):
     ids = ids[::-1]
     wide, id_log = gather(table, ids, n_keys=20)
     check(table, ids, wide, id_log, 20)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("dim", WIDE_DIMS)
+def test_rows_wider_than_one_workgroup(dtype, dim):
+    """blockIdx.x >= 1, for R = 1, 3 and 8: every chunk of the row arrives, the poison behind dim survives, and the log still
+    gets ONE entry per row"""
+    vocab = 37
+    table = _table(dtype, vocab, dim)
+    for R in (1, 3, 8):
+        ids = [(vocab - 1) * r // max(R - 1, 1) for r in range(R)] if R > 1 else [vocab // 3]
+        ids = ids[::-1]
+        wide, id_log = gather(table, ids, n_keys=20)
+        check(table, ids, wide, id_log, 20)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)

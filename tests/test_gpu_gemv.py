@@ -4,6 +4,8 @@ checker is the float64 product, the tolerance what one rounding to the output dt
 import pytest
 import torch
 
+import gemv_exact_cases as exact
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 torch.set_grad_enabled(False)
@@ -26,6 +28,22 @@ def test_gemv_equals_the_float64_product(dtype, M, N, K):
     # and next to the op it replaces
     ref = x @ w.t()
     assert float((got.float() - ref.float()).abs().max()) <= 4 * eps * float(want.abs().max()) + 1e-6
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("M", exact.EVERY_M, ids=lambda M: f"M{M}")
+def test_integer_operands_give_the_bits_of_the_exact_product(dtype, M):
+    """every M of the launch's switch, each at every shape tests/gemv_exact_cases.py lists for it; the fp32 sums are exact in any
+    order, so the checker is the int64 product on the CPU rounded once, and the comparison is bit for bit"""
+    from mquant_amd import ops
+    shapes = exact.cases_of(M, mirrored=False)
+    assert len(shapes) >= 3
+    for _, N, K, _ in shapes:
+        x, w, want, _ = exact.case(dtype, M, N, K)
+        out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)      # a row the launch forgets stays NaN
+        got = ops.gemv_f16(x.to(DEV), w.to(DEV), out=out)
+        assert got.data_ptr() == out.data_ptr()
+        assert exact.same_bits(got, want), (N, K, float((got.float().cpu() - want.float()).abs().max()))
 
 
 def test_strided_operands_and_out_buffer():

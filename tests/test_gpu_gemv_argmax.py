@@ -3,7 +3,9 @@ the device.  Two exact contracts, so every comparison is exact:
 
   * logits, when asked for, are the bits ``ops.gemv_f16`` writes for the same arguments;
   * token[m] is the argmax of THOSE 16-bit values as the CPU ``torch.argmax`` defines it (lowest index among equals, -0 == +0, a
-    NaN is maximal and the first NaN wins): ``torch.argmax(ops.gemv_f16(x, w).cpu(), dim=1)`` is the checker throughout.
+    NaN is maximal and the first NaN wins): ``torch.argmax(ops.gemv_f16(x, w).cpu(), dim=1)`` is the checker of every test but
+    one -- the integer-valued operands of tests/gemv_exact_cases.py have a checker that never calls the kernel (the int64 product
+    of the CPU, rounded once), since a fault shared by the two instantiations of the one template is invisible to the first.
 
 Rows of W go to waves four at a time, wave by wave, workgroup = four waves (rows [16 b, 16 b + 16) of pass 0 belong to workgroup b);
 a matrix with more rows than the grid's waves x 4 takes further passes (70001 rows: three on a 256-CU chip).  The planted cases
@@ -12,6 +14,8 @@ import functools
 
 import pytest
 import torch
+
+import gemv_exact_cases as exact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -72,6 +76,33 @@ def test_random_data(dtype, M, N, K):
     tok2 = ops.gemv_f16_argmax(x, w, logits=logits)
     assert same_bits(logits, ref) and torch.equal(tok2.cpu().long(), want)
     assert bool((poison == 7.0).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("M", exact.EVERY_M, ids=lambda M: f"M{M}")
+def test_integer_operands_against_a_checker_that_is_not_the_kernel(dtype, M):
+    """Every M of the launch's switch, each at every shape tests/gemv_exact_cases.py lists for it (the mirrored ones, where every
+    maximum is a tie, included), with operands whose fp32 sums are exact in any order: the logits are the int64 product of the CPU
+    rounded once, the tokens ``torch.argmax`` of THOSE values -- ``gemv_f16`` is one of the three calls under test here, not the
+    checker."""
+    from mquant_amd import ops
+    shapes = exact.cases_of(M)
+    assert len(shapes) >= 3
+    for _, N, K, mirrored in shapes:
+        what = (N, K, mirrored)
+        x, w, want, want_tok = exact.case(dtype, M, N, K, mirrored)
+        x, w = x.to(DEV), w.to(DEV)
+        ref = ops.gemv_f16(x, w, out=torch.full((M, N), float("nan"), dtype=dtype, device=DEV))
+        assert exact.same_bits(ref, want), what
+        tok = torch.full((M,), -77, dtype=torch.int32, device=DEV)          # a row the launch forgets stays -77
+        ops.gemv_f16_argmax(x, w, token_out=tok)                            # logits=None
+        print(what, "tokens", tok.cpu().tolist(), "checker", want_tok.tolist())
+        assert torch.equal(tok.cpu().long(), want_tok), what
+        tok2 = torch.full((M,), -77, dtype=torch.int32, device=DEV)
+        logits = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
+        ops.gemv_f16_argmax(x, w, logits=logits, token_out=tok2)
+        assert same_bits(logits, ref) and exact.same_bits(logits, want), what
+        assert torch.equal(tok2.cpu().long(), want_tok), what
 
 
 def test_the_last_shape_takes_more_than_one_pass():

@@ -400,6 +400,23 @@ int mq_attn_decode_fp8kv_quant_i8(const void *q, int dtype, int R, long T, const
                                   long ldq, const uint8_t *kv_cache, long ldkv, const float *kv_scale, float softmax_scale, int causal,
                                   float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
                                   void *workspace, size_t workspace_bytes, void *stream);
+/* The same two calls over a 16-BIT cache (the reference's default: k_bits = v_bits = 16 leave K / V as they are): kv_cache is
+ * [T][ldkv] ELEMENTS of `dtype`, per token the K heads then the V heads -- the e4m3 layout at two bytes per element, what
+ * mq_kv_append_rope writes and what mq_attn_prefill reads with k = kv_cache, v = kv_cache + kv_heads * head_dim -- and there are
+ * no scales:
+ *     O[r][h][:] = softmax_k((Q[r][h] . K[k][g]) * softmax_scale) @ V[k][g]
+ * Everything else is as above -- n, the clamp, causal, the strides, the workspace, the plan (it does not depend on the storage) --
+ * and so is the arithmetic: the e4m3 kernel with both scales 1.0f, so equal cache VALUES give equal bits.  (T + 32) * ldkv * 2 must
+ * stay below 4 GiB.  No reference counterpart, parity unpinned; checker = float64 softmax attention over the cache,
+ * tests/attn_decode_reference.py. */
+int mq_attn_decode(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
+                   long ldq, const void *kv_cache, long ldkv, float softmax_scale, int causal,
+                   void *out, long ldo, void *workspace, size_t workspace_bytes, void *stream);
+/* ... with the fused int8 quantizer of mq_attn_decode_fp8kv_quant_i8 (checker = mq_quantize_act_i8 of mq_attn_decode's output). */
+int mq_attn_decode_quant_i8(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
+                            long ldq, const void *kv_cache, long ldkv, float softmax_scale, int causal,
+                            float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
+                            void *workspace, size_t workspace_bytes, void *stream);
 /* Bytes of workspace the plan of such a call needs: 0 when the keys are not split.  Host arithmetic only (0 also for arguments the
  * call would refuse). */
 size_t mq_attn_decode_workspace_bytes(int R, long T, int heads, int kv_heads);
@@ -438,6 +455,15 @@ int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_
                           int heads, int kv_heads, int head_dim, long ldqkv,
                           const void *cos, const void *sin, long table_rows,
                           uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream);
+/* The launch in front of mq_attn_decode: mq_kv_append_rope_fp8 word for word -- the same n, t and p, the same two clamps, the same
+ * append-only mode -- into a 16-BIT cache ([T][ldkv] elements of `dtype`): cache row t receives the BITS of the rotated, rounded K
+ * heads and then the bits of the V heads; nothing is quantised and there are no scales (checker = mq_rope_inplace, then a copy).
+ * The V columns of qkv and every cache byte outside row t's 2 * kv_heads * head_dim elements are not written.  head_dim a multiple
+ * of 16; qkv rows, the tables and the cache rows 16-byte aligned. */
+int mq_kv_append_rope(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                      int heads, int kv_heads, int head_dim, long ldqkv,
+                      const void *cos, const void *sin, long table_rows,
+                      void *kv_cache, long ldkv, void *stream);
 
 /* out[m][n] = sum_k x[m][k] * W[n][k], 16-bit x ([M <= 8, K], ldx elements per row) and W ([N, K], ldw), fp32 products and sums,
  * one rounding to the same 16-bit dtype: the UNQUANTIZED lm_head on the last position(s) of a prefill (the reference leaves

@@ -36,6 +36,16 @@
 // row at or beyond n comes back as zeros from the hardware's range check whatever it holds (a 0x7F byte is a NaN, and 0 x NaN
 // would be one too); the next block is in flight while the current one is multiplied.  S is computed transposed (lane = M row),
 // so the softmax statistics are lane-local; columns 16 .. 31 of the 32-wide tile carry zero queries and are never stored.
+//
+// The same kernel serves a 16-BIT cache (mq_attn_decode, mq_attn_decode_quant_i8: the reference's default k_bits = v_bits = 16):
+// the storage is the kernel's second template parameter KVB, the bytes of a cache element.  KVB = 2 is the layout above at two
+// bytes per element in q's dtype, and only the LOAD side differs: a lane's K piece is 128 contiguous bytes -- eight 16-byte
+// loads that ARE the eight MFMA operands -- its V piece another 128 that go to the LDS tile where widen16 puts the same values,
+// and there are no scales: the score and output factors are the expressions above with both scales 1.0f, so the two storages
+// give equal bits on equal values.  Everything after the loads is the same source.  What is in flight differs: sixteen 16-byte
+// loads per lane next to the eight K operands in use do not fit the 256 registers of two workgroups per CU, so the 16-bit path
+// prefetches the next block's K only (issued once S has consumed the operands, in flight during the softmax and P V) and
+// loads the CURRENT block's V at the top of the iteration, in flight during S -- its registers are then free for P V.
 #include "attn_common.h"
 
 namespace mq {
@@ -51,8 +61,8 @@ constexpr int AD_PART = AD_D + 2;                // floats of one partial state:
 
 struct AttnDecArgs {
     const void *q;             // [R, heads * 128] (row stride ldq elements), fp16 / bf16
-    const uint8_t *kv;         // e4m3 cache: [T][ldkv] bytes, per token the K heads, then the V heads
-    const float *kv_scale;     // [2 * kv_heads]
+    const uint8_t *kv;         // cache: [T][ldkv] elements (e4m3 bytes, or q's dtype), per token the K heads, then the V heads
+    const float *kv_scale;     // [2 * kv_heads]; null for a 16-bit cache (no scales: both factors 1)
     const int32_t *n_dev;      // optional device-side key count
     void *out;                 // [R, heads * 128] (row stride ldo elements), q's dtype
     float *ws;                 // splits > 1: acc [splits][R * heads][128], then ml [splits][R * heads][2]
@@ -100,7 +110,7 @@ __device__ __forceinline__ void decode_store4(const AttnDecArgs &p, long row, lo
     }
 }
 
-template <int DT>
+template <int DT, int KVB>
 __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs p)
 {
     kernarg_warm<sizeof(AttnDecArgs)>();
@@ -117,23 +127,37 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
     const int n_blocks = (int)((k1 - k0 + AD_KB - 1) / AD_KB);
 
     const int ko = lane >> 5;                                         // lane half: d 64 ko.. of K / Q, keys + 4 ko of S, octet ko of P
-    const float sc = p.kv_scale[kvh] * p.softmax_scale * 1.4426950408889634f;   // K scale and log2(e) folded into the score scale
-    const float s_v = p.kv_scale[p.kv_heads + kvh];
+    const float s_k = KVB == 1 ? p.kv_scale[kvh] : 1.0f;
+    const float sc = s_k * p.softmax_scale * 1.4426950408889634f;     // K scale and log2(e) folded into the score scale
+    const float s_v = KVB == 1 ? p.kv_scale[p.kv_heads + kvh] : 1.0f;
     char *vt = smem + wave * AD_WAVE_LDS;                             // this wave's V tile: [32 keys] rows of 256 bytes, swizzled
     float *stats = reinterpret_cast<float *>(smem + AD_NW * AD_WAVE_LDS);
 
-    // K / V of this kv head, keys [0, n): rows at or beyond n answer zero (see the head of the file); host: (T + 32) ldkv < 2^32
-    const unsigned ldkv = (unsigned)p.ldkv, kv_bytes = (unsigned)(n - 1) * ldkv + AD_D;
-    const __amdgpu_buffer_rsrc_t k_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.kv) + (long)kvh * AD_D, 0, kv_bytes, 0x00020000);
+    // K / V of this kv head, keys [0, n): rows at or beyond n answer zero (see the head of the file).  Everything here is in
+    // BYTES (a head is AD_D * KVB of them); host: (T + 32) x the row stride in bytes < 2^32
+    constexpr int NL = 4 * KVB;                                       // 16-byte loads of a lane's K piece, and of its V piece
+    const unsigned ldkv = (unsigned)p.ldkv * KVB, kv_bytes = (unsigned)(n - 1) * ldkv + AD_D * KVB;
+    const __amdgpu_buffer_rsrc_t k_rs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.kv) + (long)kvh * AD_D * KVB, 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t v_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.kv) + (long)(p.kv_heads + kvh) * AD_D, 0, kv_bytes, 0x00020000);
-    // K: the 64 bytes d 64 ko.. of key (lane & 31), straight into MFMA operands; V: the 64 bytes d 64 (lane & 1).. of key lane / 2
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.kv) + (long)(p.kv_heads + kvh) * AD_D * KVB, 0, kv_bytes, 0x00020000);
+    // K: the 64 values d 64 ko.. of key (lane & 31), straight into MFMA operands; V: the 64 values d 64 (lane & 1).. of key lane / 2
     const int v_key = lane >> 1, v_d = (lane & 1) * 64;
-    const unsigned off_k = (unsigned)(lane & 31) * ldkv + 64 * ko, off_v = (unsigned)v_key * ldkv + v_d;
-    auto load_block = [&](int kb, v4i (&kraw)[4], v4i (&vraw)[4]) {
+    const unsigned off_k = (unsigned)(lane & 31) * ldkv + 64 * KVB * ko, off_v = (unsigned)v_key * ldkv + v_d * KVB;
+    auto load_k = [&](int kb, v4i (&kraw)[NL]) {
         const unsigned blk = (unsigned)(k0 + (long)kb * AD_KB) * ldkv;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < NL; ++j) kraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(k_rs, blk + off_k, 16 * j, 0));
+    };
+    auto load_v = [&](int kb, v4i (&vraw)[NL]) {
+        const unsigned blk = (unsigned)(k0 + (long)kb * AD_KB) * ldkv;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) vraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(v_rs, blk + off_v, 16 * j, 0));
+    };
+    auto load_block = [&](int kb, v4i (&kraw)[NL], v4i (&vraw)[NL]) {
+        const unsigned blk = (unsigned)(k0 + (long)kb * AD_KB) * ldkv;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
             kraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(k_rs, blk + off_k + 16 * j, 0, 0));
             vraw[j] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(v_rs, blk + off_v + 16 * j, 0, 0));
         }
@@ -160,22 +184,32 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
             for (int e = 0; e < 16; ++e) O[dt][e] = 0.0f;
         float m_run = -1.0e30f, l_run = 0.0f;                          // log2 domain
 
-        v4i kraw[4], vraw[4];
-        if (wave < n_blocks) load_block(wave, kraw, vraw);
+        v4i kraw[NL], vraw[NL];
+        if (wave < n_blocks) {
+            if constexpr (KVB == 1) load_block(wave, kraw, vraw);
+            else load_k(wave, kraw);
+        }
         for (int kb = wave; kb < n_blocks; kb += AD_NW) {
-            // ---- K into MFMA operands, V into this wave's LDS tile, both widened on the way ----------------------------
+            // ---- K into MFMA operands, V into this wave's LDS tile; e4m3 is widened on the way, 16-bit values go as they are
             v4i Kf[8];
+            if constexpr (KVB == 1) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) widen16<DT>(kraw[j], Kf[2 * j], Kf[2 * j + 1]);
+                for (int j = 0; j < 4; ++j) widen16<DT>(kraw[j], Kf[2 * j], Kf[2 * j + 1]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v4i a, b;
-                widen16<DT>(vraw[j], a, b);
-                const int c = ((v_d + 16 * j) * 2) ^ ((v_key & 3) << 5);      // 32 B = sixteen values = one swizzle group
-                *reinterpret_cast<v4i *>(vt + v_key * AD_VROW + c) = a;
-                *reinterpret_cast<v4i *>(vt + v_key * AD_VROW + c + 16) = b;
+                for (int j = 0; j < 4; ++j) {
+                    v4i a, b;
+                    widen16<DT>(vraw[j], a, b);
+                    const int c = ((v_d + 16 * j) * 2) ^ ((v_key & 3) << 5);      // 32 B = sixteen values = one swizzle group
+                    *reinterpret_cast<v4i *>(vt + v_key * AD_VROW + c) = a;
+                    *reinterpret_cast<v4i *>(vt + v_key * AD_VROW + c + 16) = b;
+                }
+            } else {
+                load_v(kb, vraw);                                                // this block's V: in flight during S
+#pragma unroll
+                for (int j = 0; j < 8; ++j) Kf[j] = kraw[j];                     // load j = the eight values d 64 ko + 8 j ..
             }
-            if (kb + AD_NW < n_blocks) load_block(kb + AD_NW, kraw, vraw);    // in flight during this block's arithmetic
+            if constexpr (KVB == 1)
+                if (kb + AD_NW < n_blocks) load_block(kb + AD_NW, kraw, vraw);    // in flight during this block's arithmetic
             const long key0 = k0 + (long)kb * AD_KB;
 
             // ---- S^T = K Q^T : [32 keys][32 columns] ---------------------------------------------------------------
@@ -184,6 +218,14 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
             for (int e = 0; e < 16; ++e) S[e] = 0.0f;
 #pragma unroll
             for (int ds = 0; ds < 8; ++ds) S = MM::mma(Kf[ds], Qf[ds], S);
+            if constexpr (KVB == 2) {
+                if (kb + AD_NW < n_blocks) load_k(kb + AD_NW, kraw);             // the next block's K: in flight from here on
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {                                    // V piece j = the eight values d 64 (lane & 1) + 8 j ..
+                    const int c = ((v_d + 8 * j) * 2) ^ ((v_key & 3) << 5);      // the swizzle moves bits 5, 6: bit 4 (odd j) stays
+                    *reinterpret_cast<v4i *>(vt + v_key * AD_VROW + c) = vraw[j];
+                }
+            }
 
             // ---- online softmax (log2 domain); register r <-> key key0 + (r & 3) + 8 (r >> 2) + 4 ko.  A key this row may
             // not see scores -inf: it leaves the maximum alone and exp2 makes it an exact 0, also where a causal row has no
@@ -315,7 +357,7 @@ __global__ __launch_bounds__(256) void attn_decode_merge_kernel(AttnDecArgs p)
     int ns = (int)((n + p.kps - 1) / p.kps);                          // the splits that hold keys; the others wrote nothing
     ns = ns < p.splits ? ns : p.splits;
     const int row = (int)(slot / p.heads), head = (int)(slot - (long)row * p.heads);
-    const float s_v = p.kv_scale[p.kv_heads + head / (p.heads / p.kv_heads)];
+    const float s_v = p.kv_scale ? p.kv_scale[p.kv_heads + head / (p.heads / p.kv_heads)] : 1.0f;      // a 16-bit cache has no scales
     const float *ml = p.ws + (long)p.splits * rows * AD_D;
     float M = -1.0e30f;
     for (int s = 0; s < ns; ++s) M = fmaxf(M, ml[((long)s * rows + slot) * 2]);
@@ -410,7 +452,8 @@ extern "C" size_t mq_attn_decode_workspace_bytes(int R, long T, int heads, int k
 }
 
 // the checks the two entry points share (the rules of mq_attn_prefill_fp8kv), then the plan and the launches
-static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int dtype, int head_dim, void *workspace, size_t workspace_bytes, void *stream)
+// kvb = bytes of a cache element: 1 = e4m3 with scales, 2 = q's dtype without
+static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int kvb, int dtype, int head_dim, void *workspace, size_t workspace_bytes, void *stream)
 {
     using namespace mq;
     constexpr int D = AD_D;
@@ -421,15 +464,15 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int dtype, int h
     AttnDecPlan pl;
     const int rc = attn_decode_plan(who, a.R, a.T, a.heads, a.kv_heads, device_cu_count(), pl);
     if (rc != MQ_OK) return rc;
-    MQ_REQUIRE(a.q && a.kv && a.kv_scale && (a.out || a.qout), "%s: null pointer", who);
+    MQ_REQUIRE(a.q && a.kv && (a.kv_scale || kvb == 2) && (a.out || a.qout), "%s: null pointer", who);
     MQ_REQUIRE(a.ldq >= (long)a.heads * D && a.ldkv >= 2L * a.kv_heads * D && (a.qout || a.ldo >= (long)a.heads * D), "%s: row strides too short", who);
-    MQ_REQUIRE(((uintptr_t)a.q) % 16 == 0 && (a.ldq * 2) % 16 == 0 && ((uintptr_t)a.kv) % 16 == 0 && a.ldkv % 16 == 0 &&
+    MQ_REQUIRE(((uintptr_t)a.q) % 16 == 0 && (a.ldq * 2) % 16 == 0 && ((uintptr_t)a.kv) % 16 == 0 && (a.ldkv * kvb) % 16 == 0 &&
                    (a.qout || (((uintptr_t)a.out) % 8 == 0 && (a.ldo * 2) % 8 == 0)),
                "%s: q / cache rows must be 16-byte aligned, out rows 8-byte aligned", who);
     MQ_REQUIRE(((uintptr_t)a.n_dev) % 4 == 0, "%s: n_keys_dev must be 4-byte aligned", who);
     // K / V are addressed through 32-bit buffer offsets (one block past the last row included)
-    MQ_REQUIRE((a.T + AD_KB) * a.ldkv < (1L << 32), "%s: (T + 32) x the cache row stride in bytes must stay below 4 GiB (T %ld, stride %ld bytes)", who, a.T,
-               a.ldkv);
+    MQ_REQUIRE(a.ldkv < (1L << 32) && (a.T + AD_KB) * a.ldkv * kvb < (1L << 32),
+               "%s: (T + 32) x the cache row stride in bytes must stay below 4 GiB (T %ld, stride %ld bytes)", who, a.T, a.ldkv * kvb);
     if (pl.ws_bytes) {
         MQ_REQUIRE(workspace && workspace_bytes >= pl.ws_bytes, "%s: %d key splits need a workspace of %zu bytes (got %zu)", who, pl.splits, pl.ws_bytes,
                    workspace ? workspace_bytes : (size_t)0);
@@ -440,8 +483,14 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int dtype, int h
     a.kps = pl.kps;
     a.passes = pl.passes;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MQ_F16) hipLaunchKernelGGL(attn_decode_kernel<MQ_F16>, dim3((unsigned)pl.grid), dim3(AD_NW * 64), 0, st, a);
-    else hipLaunchKernelGGL(attn_decode_kernel<MQ_BF16>, dim3((unsigned)pl.grid), dim3(AD_NW * 64), 0, st, a);
+    const dim3 grid((unsigned)pl.grid), block(AD_NW * 64);
+    if (kvb == 1) {
+        if (dtype == MQ_F16) hipLaunchKernelGGL((attn_decode_kernel<MQ_F16, 1>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_decode_kernel<MQ_BF16, 1>), grid, block, 0, st, a);
+    } else {
+        if (dtype == MQ_F16) hipLaunchKernelGGL((attn_decode_kernel<MQ_F16, 2>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_decode_kernel<MQ_BF16, 2>), grid, block, 0, st, a);
+    }
     int lrc = check_launch("attn_decode");
     if (lrc != MQ_OK || pl.splits == 1) return lrc;
     const dim3 mgrid((unsigned)((a.R * a.heads + 7) / 8));
@@ -450,15 +499,35 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int dtype, int h
     return check_launch("attn_decode_merge");
 }
 
+// the arguments the entry points share, and those of the fused quantizer (checked under the entry point's name)
+static mq::AttnDecArgs attn_decode_args(const void *q, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, long ldq, const void *kv_cache,
+                                        long ldkv, const float *kv_scale, float softmax_scale, int causal, void *out, long ldo)
+{
+    mq::AttnDecArgs a{};
+    a.q = q; a.kv = reinterpret_cast<const uint8_t *>(kv_cache); a.kv_scale = kv_scale; a.n_dev = n_keys_dev; a.out = out; a.T = T; a.ldq = ldq;
+    a.ldkv = ldkv; a.ldo = ldo; a.R = R; a.heads = heads; a.kv_heads = kv_heads; a.causal = causal ? 1 : 0; a.softmax_scale = softmax_scale;
+    a.qs0 = a.qs1 = a.qi0 = a.qi1 = 1.0f;
+    return a;
+}
+
+static int attn_decode_quant_args(const char *who, mq::AttnDecArgs &a, float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo)
+{
+    using namespace mq;
+    a.qout = out; a.q_kpad = K_pad; a.q_ld = ldo; a.qs0 = scale0; a.qs1 = scale1; a.row_sel = row_sel;
+    MQ_REQUIRE(a.heads >= 1 && K_pad == (long)a.heads * AD_D && K_pad % 64 == 0 && ((uintptr_t)out) % 16 == 0 && (ldo == MQ_LD_TILED || (ldo >= K_pad && ldo % 4 == 0)),
+               "%s: out must hold exactly heads * head_dim = %ld columns (K_pad %ld, a multiple of 64), ldo = MQ_LD_TILED or a row stride", who,
+               (long)a.heads * AD_D, K_pad);
+    MQ_REQUIRE(scale0 > 0.0f && scale1 > 0.0f, "%s: scales must be positive", who);
+    a.qi0 = 1.0f / scale0; a.qi1 = 1.0f / scale1; a.qr0 = quant_rcp_ok(scale0) ? 1 : 0; a.qr1 = quant_rcp_ok(scale1) ? 1 : 0;
+    return MQ_OK;
+}
+
 extern "C" int mq_attn_decode_fp8kv(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
                                     long ldq, const uint8_t *kv_cache, long ldkv, const float *kv_scale, float softmax_scale, int causal,
                                     void *out, long ldo, void *workspace, size_t workspace_bytes, void *stream)
 {
-    mq::AttnDecArgs a{};
-    a.q = q; a.kv = kv_cache; a.kv_scale = kv_scale; a.n_dev = n_keys_dev; a.out = out; a.T = T; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo;
-    a.R = R; a.heads = heads; a.kv_heads = kv_heads; a.causal = causal ? 1 : 0; a.softmax_scale = softmax_scale;
-    a.qs0 = a.qs1 = a.qi0 = a.qi1 = 1.0f;
-    return attn_decode_run("mq_attn_decode_fp8kv", a, dtype, head_dim, workspace, workspace_bytes, stream);
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, kv_scale, softmax_scale, causal, out, ldo);
+    return attn_decode_run("mq_attn_decode_fp8kv", a, 1, dtype, head_dim, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_attn_decode_fp8kv_quant_i8(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
@@ -466,15 +535,28 @@ extern "C" int mq_attn_decode_fp8kv_quant_i8(const void *q, int dtype, int R, lo
                                              float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
                                              void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace mq;
-    AttnDecArgs a{};
-    a.q = q; a.kv = kv_cache; a.kv_scale = kv_scale; a.n_dev = n_keys_dev; a.out = nullptr; a.T = T; a.ldq = ldq; a.ldkv = ldkv; a.ldo = 0;
-    a.R = R; a.heads = heads; a.kv_heads = kv_heads; a.causal = causal ? 1 : 0; a.softmax_scale = softmax_scale;
-    a.qout = out; a.q_kpad = K_pad; a.q_ld = ldo; a.qs0 = scale0; a.qs1 = scale1; a.row_sel = row_sel;
-    MQ_REQUIRE(heads >= 1 && K_pad == (long)heads * AD_D && K_pad % 64 == 0 && ((uintptr_t)out) % 16 == 0 && (ldo == MQ_LD_TILED || (ldo >= K_pad && ldo % 4 == 0)),
-               "mq_attn_decode_fp8kv_quant_i8: out must hold exactly heads * head_dim = %ld columns (K_pad %ld, a multiple of 64), ldo = MQ_LD_TILED or a row stride",
-               (long)heads * AD_D, K_pad);
-    MQ_REQUIRE(scale0 > 0.0f && scale1 > 0.0f, "mq_attn_decode_fp8kv_quant_i8: scales must be positive");
-    a.qi0 = 1.0f / scale0; a.qi1 = 1.0f / scale1; a.qr0 = quant_rcp_ok(scale0) ? 1 : 0; a.qr1 = quant_rcp_ok(scale1) ? 1 : 0;
-    return attn_decode_run("mq_attn_decode_fp8kv_quant_i8", a, dtype, head_dim, workspace, workspace_bytes, stream);
+    const char *who = "mq_attn_decode_fp8kv_quant_i8";
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, kv_scale, softmax_scale, causal, nullptr, 0);
+    const int rc = attn_decode_quant_args(who, a, scale0, scale1, row_sel, out, K_pad, ldo);
+    return rc != MQ_OK ? rc : attn_decode_run(who, a, 1, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+// ---- the same two calls over a 16-bit cache: kv_cache in q's dtype, ldkv in elements, no scales ----
+extern "C" int mq_attn_decode(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim, long ldq,
+                              const void *kv_cache, long ldkv, float softmax_scale, int causal, void *out, long ldo, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, nullptr, softmax_scale, causal, out, ldo);
+    return attn_decode_run("mq_attn_decode", a, 2, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_attn_decode_quant_i8(const void *q, int dtype, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads, int head_dim,
+                                       long ldq, const void *kv_cache, long ldkv, float softmax_scale, int causal, float scale0, float scale1,
+                                       const uint8_t *row_sel, int8_t *out, long K_pad, long ldo, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    const char *who = "mq_attn_decode_quant_i8";
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, nullptr, softmax_scale, causal, nullptr, 0);
+    const int rc = attn_decode_quant_args(who, a, scale0, scale1, row_sel, out, K_pad, ldo);
+    return rc != MQ_OK ? rc : attn_decode_run(who, a, 2, dtype, head_dim, workspace, workspace_bytes, stream);
 }

@@ -21,6 +21,11 @@
 // every lane of which receives the same dword), as in attn_decode.hip.  One lane = eight rotate-half pairs of a Q or K head
 // (two 16-byte loads and stores; a K lane also stores two 8-byte groups of e4m3) or sixteen elements of a V head (two 16-byte
 // loads, two 8-byte stores).  The grid depends on R, heads, kv_heads and head_dim only -- never on n.
+//
+// mq_kv_append_rope is the same launch for a 16-BIT cache (the reference's default k_bits = v_bits = 16; what mq_attn_decode
+// reads): the store is the kernel's second template parameter KVB, the bytes of a cache element.  With KVB = 2 nothing is
+// quantised -- cache row t receives the BITS of the rotated, rounded K heads and of the V heads -- and the lane-to-element map
+// is the same: a K lane stores its two 16-byte pieces, a V lane its two.
 #include "kv_rope_common.h"
 
 namespace mq {
@@ -28,8 +33,8 @@ namespace mq {
 struct KvAppendArgs {
     void *qkv;                 // [R][ldqkv]: per row `heads` Q heads, kv_heads K heads, kv_heads V heads
     const void *cos, *sin;     // [table_rows][head_dim], or both null: append only
-    uint8_t *kv;               // e4m3 cache: [T][ldkv] bytes, per token the K heads, then the V heads
-    const float *kv_scale;     // [2 * kv_heads]
+    uint8_t *kv;               // cache: [T][ldkv] elements (e4m3 bytes, or qkv's dtype), per token the K heads, then the V heads
+    const float *kv_scale;     // [2 * kv_heads]; null for a 16-bit cache
     const int32_t *n_dev;      // optional device-side key count (after the append)
     const int32_t *delta_dev;  // optional device-side RoPE position offset
     long T, ldqkv, ldkv, table_rows;
@@ -46,7 +51,15 @@ __device__ __forceinline__ v2i append_quant8(const v8us &x, float s)
     return kv_quant8_e4m3(v, s);
 }
 
-template <int DT>
+// eight elements of a cache row at element offset `at`: quantised to e4m3 with the head's scale, or their bits as they are
+template <int DT, int KVB>
+__device__ __forceinline__ void append_store8(uint8_t *crow, long at, const v8us &x, float s)
+{
+    if constexpr (KVB == 1) *reinterpret_cast<v2i *>(crow + at) = append_quant8<DT>(x, s);
+    else *reinterpret_cast<v8us *>(crow + at * 2) = x;
+}
+
+template <int DT, int KVB>
 __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
 {
     kernarg_warm<sizeof(KvAppendArgs)>();
@@ -68,16 +81,16 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
     const long t = n - p.R + r;
     const int D = p.head_dim, half = D / 2, qk = p.heads + p.kv_heads;
     E *row = reinterpret_cast<E *>(p.qkv) + (long)r * p.ldqkv;
-    uint8_t *crow = p.kv + t * p.ldkv;
+    uint8_t *crow = p.kv + t * p.ldkv * KVB;
 
-    if ((int)hh >= qk) {                                              // ---- V: sixteen consecutive elements, quantised as they are
+    if ((int)hh >= qk) {                                              // ---- V: sixteen consecutive elements, stored as they are
         const int vh = p.kv_heads + ((int)hh - qk);                   // head of the cache row
         const E *src = row + (long)hh * D + g * 16;
         const v8us x0 = *reinterpret_cast<const v8us *>(src), x1 = *reinterpret_cast<const v8us *>(src + 8);
-        const float s = p.kv_scale[vh];
-        uint8_t *dst = crow + (long)vh * D + g * 16;
-        *reinterpret_cast<v2i *>(dst) = append_quant8<DT>(x0, s);
-        *reinterpret_cast<v2i *>(dst + 8) = append_quant8<DT>(x1, s);
+        const float s = KVB == 1 ? p.kv_scale[vh] : 1.0f;
+        const long at = (long)vh * D + g * 16;
+        append_store8<DT, KVB>(crow, at, x0, s);
+        append_store8<DT, KVB>(crow, at + 8, x1, s);
         return;
     }
     const bool rotate = p.cos != nullptr;
@@ -100,22 +113,22 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
     }
     if ((int)hh >= p.heads) {                                         // ---- K: the two halves of the rotated head
         const int kh = (int)hh - p.heads;
-        const float s = p.kv_scale[kh];
-        uint8_t *dst = crow + (long)kh * D + g * 8;
-        *reinterpret_cast<v2i *>(dst) = append_quant8<DT>(a8, s);
-        *reinterpret_cast<v2i *>(dst + half) = append_quant8<DT>(b8, s);
+        const float s = KVB == 1 ? p.kv_scale[kh] : 1.0f;
+        const long at = (long)kh * D + g * 8;
+        append_store8<DT, KVB>(crow, at, a8, s);
+        append_store8<DT, KVB>(crow, at + half, b8, s);
     }
 }
 
 }  // namespace mq
 
-extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
-                                     int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
-                                     uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream)
+// the checks and the launch of both entry points; kvb = bytes of a cache element: 1 = e4m3 with scales, 2 = qkv's dtype without
+static int kv_append_run(const char *who, const char *kernel, int kvb, void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev,
+                         const int32_t *rope_delta_dev, int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin,
+                         long table_rows, void *kv_cache, long ldkv, const float *kv_scale, void *stream)
 {
     using namespace mq;
-    const char *who = "mq_kv_append_rope_fp8";
-    MQ_REQUIRE(qkv && kv_cache && kv_scale, "%s: null pointer", who);
+    MQ_REQUIRE(qkv && kv_cache && (kv_scale || kvb == 2), "%s: null pointer", who);
     MQ_REQUIRE(dtype == MQ_F16 || dtype == MQ_BF16, "%s: qkv dtype must be fp16 or bf16 (got %d)", who, dtype);
     MQ_REQUIRE(R >= 1 && R <= 8, "%s: R = %d new rows (1 .. 8)", who, R);
     MQ_REQUIRE(T >= R, "%s: T = %ld cache rows for R = %d new rows (the rows are the last R positions: T >= R)", who, T, R);
@@ -126,7 +139,8 @@ extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const 
     MQ_REQUIRE(ldqkv >= cols, "%s: qkv row stride %ld shorter than (heads + 2 kv_heads) * head_dim = %ld", who, ldqkv, cols);
     MQ_REQUIRE(((uintptr_t)qkv) % 16 == 0 && (ldqkv * 2) % 16 == 0, "%s: qkv rows must be 16-byte aligned", who);
     MQ_REQUIRE(ldkv >= 2L * kv_heads * head_dim, "%s: cache row stride %ld shorter than 2 kv_heads * head_dim = %ld", who, ldkv, 2L * kv_heads * head_dim);
-    MQ_REQUIRE(((uintptr_t)kv_cache) % 8 == 0 && ldkv % 8 == 0, "%s: cache rows must be 8-byte aligned", who);
+    const int align = 8 * kvb;                                         // of a lane's stores: eight cache elements
+    MQ_REQUIRE(((uintptr_t)kv_cache) % align == 0 && ldkv % 8 == 0, "%s: cache rows must be %d-byte aligned", who, align);
     MQ_REQUIRE((cos == nullptr) == (sin == nullptr), "%s: cos and sin must both be given or both be null (append only)", who);
     if (cos) {
         MQ_REQUIRE(table_rows >= 1, "%s: table_rows = %ld (at least one row of cos / sin)", who, table_rows);
@@ -135,11 +149,33 @@ extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const 
     MQ_REQUIRE(((uintptr_t)n_keys_dev) % 4 == 0, "%s: n_keys_dev must be 4-byte aligned", who);
     MQ_REQUIRE(((uintptr_t)rope_delta_dev) % 4 == 0, "%s: rope_delta_dev must be 4-byte aligned", who);
 
-    KvAppendArgs a{qkv, cos, sin, kv_cache, kv_scale, n_keys_dev, rope_delta_dev, T, ldqkv, ldkv, table_rows, R, heads, kv_heads, head_dim};
+    KvAppendArgs a{qkv, cos, sin, reinterpret_cast<uint8_t *>(kv_cache), kv_scale, n_keys_dev, rope_delta_dev, T, ldqkv, ldkv, table_rows, R, heads, kv_heads,
+                   head_dim};
     const unsigned lanes = (unsigned)(R * (cols / 16));
     const dim3 grid((lanes + 255) / 256);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MQ_F16) hipLaunchKernelGGL(kv_append_rope_kernel<MQ_F16>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(kv_append_rope_kernel<MQ_BF16>, grid, dim3(256), 0, st, a);
-    return check_launch("kv_append_rope_fp8");
+    if (kvb == 1) {
+        if (dtype == MQ_F16) hipLaunchKernelGGL((kv_append_rope_kernel<MQ_F16, 1>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((kv_append_rope_kernel<MQ_BF16, 1>), grid, dim3(256), 0, st, a);
+    } else {
+        if (dtype == MQ_F16) hipLaunchKernelGGL((kv_append_rope_kernel<MQ_F16, 2>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((kv_append_rope_kernel<MQ_BF16, 2>), grid, dim3(256), 0, st, a);
+    }
+    return check_launch(kernel);
+}
+
+extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                                     int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
+                                     uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream)
+{
+    return kv_append_run("mq_kv_append_rope_fp8", "kv_append_rope_fp8", 1, qkv, dtype, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv,
+                         cos, sin, table_rows, kv_cache, ldkv, kv_scale, stream);
+}
+
+extern "C" int mq_kv_append_rope(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev, int heads,
+                                 int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows, void *kv_cache,
+                                 long ldkv, void *stream)
+{
+    return kv_append_run("mq_kv_append_rope", "kv_append_rope", 2, qkv, dtype, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv, cos, sin,
+                         table_rows, kv_cache, ldkv, nullptr, stream);
 }

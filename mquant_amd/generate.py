@@ -1,6 +1,6 @@
 """A greedy generation loop that never leaves the device: the step feeds itself.
 
-``Fp8KVCache`` made the middle of a generation step capturable (its length lives on the device); ``GreedyLoop`` closes both ends with
+``Fp8KVCache`` and ``KVCache16`` made the middle of a generation step capturable (the length lives on the device); ``GreedyLoop`` closes both ends with
 ONE int32 ``token`` on the device, as ``n_keys`` already is:
 
     cache.advance(1)                                             # n_keys += 1
@@ -14,19 +14,20 @@ which is indexed by cache position -- one copy, the single synchronisation.  Gre
 (inspect the ids between batches of replays)."""
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, Optional, Union
 
 import torch
 import torch.nn.functional as F
 
 from . import ops
-from .kv_cache import Fp8KVCache
+from .kv_cache import Fp8KVCache, KVCache16
 
 
 class GreedyLoop:
-    def __init__(self, cache: Fp8KVCache, embed_tokens: torch.Tensor, lm_head: torch.Tensor,
+    def __init__(self, cache: Union[Fp8KVCache, KVCache16], embed_tokens: torch.Tensor, lm_head: torch.Tensor,
                  body: Callable[[torch.Tensor], torch.Tensor], eps: float = 1e-6):
-        """embed_tokens [vocab, dim] and lm_head [vocab_out, dim]: fp16 / bf16 CUDA tensors of the cache's dtype.  body: hidden
+        """cache: either cache class -- the loop touches ``dtype``, ``capacity``, ``n_keys``, ``caches``, ``advance`` and ``set_length``
+        only, and the body calls the cache's own ``step``.  embed_tokens [vocab, dim] and lm_head [vocab_out, dim]: fp16 / bf16 CUDA tensors of the cache's dtype.  body: hidden
         [1, dim] -> [1, dim], the decoder layers of ONE new position; for a step that is to be captured it must neither synchronise
         nor depend on host state that changes between steps."""
         assert embed_tokens.dim() == 2 and lm_head.dim() == 2 and embed_tokens.shape[1] == lm_head.shape[1]

@@ -10,7 +10,11 @@ layers ONE int32 ``n_keys`` on the device -- the number of cache rows that hold 
 where ``step`` is two native calls that both read ``n_keys`` themselves: ``ops.kv_append_rope_fp8`` (rotate Q and K, quantise K|V
 into rows [n - R, n)) and ``ops.attn_decode_fp8kv``.  The class keeps NO host copy of the length: after one warm-up step (the
 decode workspace and the one-time check of the scales happen there) ``advance`` and ``step`` with ``out`` given neither
-synchronise nor allocate, so the step is captured once into a graph and replayed while the cache grows."""
+synchronise nor allocate, so the step is captured once into a graph and replayed while the cache grows.
+
+``KVCache16`` is the same object for the reference's default KV setting (``--k_bits 16 --v_bits 16``: K / V stay in the model's
+dtype): the caches hold ``dtype`` instead of e4m3, there are no scales, and ``step`` is ``ops.kv_append_rope`` and
+``ops.attn_decode``.  Same interface, same contract; what does not depend on the storage lives in one base class."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -20,38 +24,27 @@ import torch
 from . import ops
 
 
-class Fp8KVCache:
-    def __init__(self, layers: int, capacity: int, kv_heads: int, head_dim: int, kv_scales: Sequence[torch.Tensor],
-                 cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], device, dtype: torch.dtype,
-                 rope_delta: Optional[int] = None):
-        """kv_scales: per layer a float32 [2 * kv_heads] tensor (K scales then V scales; a [layers, 2 * kv_heads] tensor works).
-        cos / sin: the RoPE tables [rows, head_dim] in ``dtype`` (contiguous), or both None for a model without rotation at this
-        point.  rope_delta: the initial position offset; None = no offset tensor at all (``set_rope_delta`` makes one later)."""
+class _DeviceLengthCache:
+    """What the two cache classes share: the geometry, the RoPE tables, the per-layer buffers and the two device integers."""
+
+    def __init__(self, layers: int, capacity: int, kv_heads: int, head_dim: int, cos: Optional[torch.Tensor],
+                 sin: Optional[torch.Tensor], device, dtype: torch.dtype, storage: torch.dtype, rope_delta: Optional[int]):
         device = torch.device(device)
-        assert len(kv_scales) == layers and (cos is None) == (sin is None)
+        assert (cos is None) == (sin is None)
         self.layers, self.capacity, self.kv_heads, self.head_dim, self.dtype = layers, capacity, kv_heads, head_dim, dtype
-        self.scales = [s.to(device=device, dtype=torch.float32).contiguous() for s in kv_scales]
-        for s in self.scales:
-            assert s.numel() == 2 * kv_heads
         if cos is not None:
             assert cos.shape == sin.shape and cos.dim() == 2 and cos.shape[1] == head_dim
             cos, sin = cos.to(device=device, dtype=dtype).contiguous(), sin.to(device=device, dtype=dtype).contiguous()
         self.cos, self.sin = cos, sin
-        self.caches = [torch.zeros((capacity, 2 * kv_heads, head_dim), dtype=torch.uint8, device=device).view(torch.float8_e4m3fn)
+        nbytes = torch.empty((), dtype=storage).element_size()
+        self.caches = [torch.zeros((capacity, 2 * kv_heads, head_dim * nbytes), dtype=torch.uint8, device=device).view(storage)
                        for _ in range(layers)]
         self.n_keys = torch.zeros((1,), dtype=torch.int32, device=device)
         self.rope_delta = None
         if rope_delta is not None:
             self.set_rope_delta(rope_delta)
 
-    # ---- host side: prefill and bookkeeping (not for a captured step) ----
-    def fill(self, layer: int, kv_cols: torch.Tensor) -> torch.Tensor:
-        """The prefill write: kv_cols [T, 2 * kv_heads, head_dim] (K already rotated; the K|V columns of the fused q|k|v output work
-        in place) into rows [0, T) of the layer's cache.  The length is set by ``set_length``, once for all layers."""
-        T = kv_cols.shape[0]
-        assert T <= self.capacity and tuple(kv_cols.shape[1:]) == (2 * self.kv_heads, self.head_dim)
-        return ops.kv_quant_fp8(kv_cols, self.scales[layer], out=self.caches[layer][:T])
-
+    # ---- host side: bookkeeping (not for a captured step) ----
     def set_length(self, n: int) -> None:
         assert 0 <= n <= self.capacity, f"length {n} outside the capacity {self.capacity}"
         self.n_keys.fill_(int(n))
@@ -67,10 +60,34 @@ class Fp8KVCache:
         """n_keys += R on the device: once per step, before the layers."""
         self.n_keys.add_(int(R))
 
+    def _q(self, qkv: torch.Tensor, heads: int) -> torch.Tensor:
+        return qkv[:, :heads * self.head_dim].view(qkv.shape[0], heads, self.head_dim)
+
+
+class Fp8KVCache(_DeviceLengthCache):
+    def __init__(self, layers: int, capacity: int, kv_heads: int, head_dim: int, kv_scales: Sequence[torch.Tensor],
+                 cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], device, dtype: torch.dtype,
+                 rope_delta: Optional[int] = None):
+        """kv_scales: per layer a float32 [2 * kv_heads] tensor (K scales then V scales; a [layers, 2 * kv_heads] tensor works).
+        cos / sin: the RoPE tables [rows, head_dim] in ``dtype`` (contiguous), or both None for a model without rotation at this
+        point.  rope_delta: the initial position offset; None = no offset tensor at all (``set_rope_delta`` makes one later)."""
+        assert len(kv_scales) == layers
+        self.scales = [s.to(device=torch.device(device), dtype=torch.float32).contiguous() for s in kv_scales]
+        for s in self.scales:
+            assert s.numel() == 2 * kv_heads
+        super().__init__(layers, capacity, kv_heads, head_dim, cos, sin, device, dtype, torch.float8_e4m3fn, rope_delta)
+
+    def fill(self, layer: int, kv_cols: torch.Tensor) -> torch.Tensor:
+        """The prefill write: kv_cols [T, 2 * kv_heads, head_dim] (K already rotated; the K|V columns of the fused q|k|v output work
+        in place) into rows [0, T) of the layer's cache.  The length is set by ``set_length``, once for all layers."""
+        T = kv_cols.shape[0]
+        assert T <= self.capacity and tuple(kv_cols.shape[1:]) == (2 * self.kv_heads, self.head_dim)
+        return ops.kv_quant_fp8(kv_cols, self.scales[layer], out=self.caches[layer][:T])
+
     def _append(self, layer: int, qkv: torch.Tensor, heads: int) -> torch.Tensor:
         ops.kv_append_rope_fp8(qkv, heads, self.caches[layer], self.scales[layer], self.cos, self.sin, n_keys=self.n_keys,
                                rope_delta=self.rope_delta)
-        return qkv[:, :heads * self.head_dim].view(qkv.shape[0], heads, self.head_dim)
+        return self._q(qkv, heads)
 
     def step(self, layer: int, qkv: torch.Tensor, heads: int, causal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """qkv [R, (heads + 2 * kv_heads) * head_dim], the raw projection of the R newest positions (``advance(R)`` came first):
@@ -83,4 +100,36 @@ class Fp8KVCache:
         """``step`` with the next Linear's static int8 quantizer fused into the attention's store (``ops.attn_decode_quant_i8``)."""
         q = self._append(layer, qkv, heads)
         return ops.attn_decode_quant_i8(q, self.caches[layer], self.scales[layer], scale0, scale1, n_keys=self.n_keys, causal=causal,
+                                        row_sel=row_sel, out=out, tiled=tiled)
+
+
+class KVCache16(_DeviceLengthCache):
+    def __init__(self, layers: int, capacity: int, kv_heads: int, head_dim: int, cos: Optional[torch.Tensor],
+                 sin: Optional[torch.Tensor], device, dtype: torch.dtype, rope_delta: Optional[int] = None):
+        """``Fp8KVCache`` without scales: the caches hold ``dtype`` (fp16 / bf16).  cos / sin, rope_delta: as there."""
+        assert dtype in (torch.float16, torch.bfloat16)
+        super().__init__(layers, capacity, kv_heads, head_dim, cos, sin, device, dtype, dtype, rope_delta)
+
+    def fill(self, layer: int, kv_cols: torch.Tensor) -> torch.Tensor:
+        """The prefill write: a bit copy of kv_cols [T, 2 * kv_heads, head_dim] (``dtype``; K already rotated; a strided view of
+        the fused q|k|v output works) into rows [0, T) of the layer's cache.  The length is set by ``set_length``."""
+        T = kv_cols.shape[0]
+        assert T <= self.capacity and tuple(kv_cols.shape[1:]) == (2 * self.kv_heads, self.head_dim) and kv_cols.dtype == self.dtype
+        self.caches[layer][:T].copy_(kv_cols)
+        return self.caches[layer][:T]
+
+    def _append(self, layer: int, qkv: torch.Tensor, heads: int) -> torch.Tensor:
+        ops.kv_append_rope(qkv, heads, self.caches[layer], self.cos, self.sin, n_keys=self.n_keys, rope_delta=self.rope_delta)
+        return self._q(qkv, heads)
+
+    def step(self, layer: int, qkv: torch.Tensor, heads: int, causal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``Fp8KVCache.step`` over the 16-bit cache: ``ops.kv_append_rope``, then ``ops.attn_decode``."""
+        q = self._append(layer, qkv, heads)
+        return ops.attn_decode(q, self.caches[layer], n_keys=self.n_keys, causal=causal, out=out)
+
+    def step_quant_i8(self, layer: int, qkv: torch.Tensor, heads: int, scale0: float, scale1: Optional[float] = None, *,
+                      causal: bool = True, row_sel: Optional[torch.Tensor] = None, out=None, tiled: bool = False):
+        """``step`` with the next Linear's static int8 quantizer fused into the attention's store (``ops.attn_decode_quant_i8``)."""
+        q = self._append(layer, qkv, heads)
+        return ops.attn_decode_quant_i8(q, self.caches[layer], None, scale0, scale1, n_keys=self.n_keys, causal=causal,
                                         row_sel=row_sel, out=out, tiled=tiled)

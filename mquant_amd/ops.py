@@ -674,14 +674,18 @@ def _decode_workspace(device, nbytes: int) -> torch.Tensor:
     return ent[0]
 
 
-def _decode_args(q, kv_cache, kv_scale, n_keys, workspace):
-    """The arguments the two decode entry points share: (R, T, n_keys_dev, heads, kv_heads, ldq, ldkv, workspace ptr, bytes)."""
+def _decode_args(q, kv_cache, kv_scale, n_keys, workspace, storage=torch.float8_e4m3fn):
+    """The arguments the decode entry points share: (R, T, n_keys_dev, heads, kv_heads, ldq, ldkv, workspace ptr, bytes).  storage:
+    the cache's dtype -- float8_e4m3fn with kv_scale, or q's dtype without (ldkv is in elements either way)."""
     R, H, D = q.shape
     cap, H2, D2 = kv_cache.shape
-    assert D2 == D and H2 % 2 == 0 and kv_cache.dtype == torch.float8_e4m3fn
+    assert D2 == D and H2 % 2 == 0 and kv_cache.dtype == storage
     assert q.stride(2) == 1 and q.stride(1) == D and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
     hkv = H2 // 2
-    _check_kv_scale(kv_scale, hkv)
+    if storage == torch.float8_e4m3fn:
+        _check_kv_scale(kv_scale, hkv)
+    else:
+        assert kv_scale is None and storage == q.dtype
     if isinstance(n_keys, torch.Tensor):
         assert n_keys.dtype == torch.int32 and n_keys.numel() == 1 and n_keys.is_cuda, "n_keys: an int or an int32 CUDA tensor of one element"
         T, n_dev = cap, n_keys.data_ptr()
@@ -718,17 +722,46 @@ def attn_decode_fp8kv(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.T
 
 
 @_on_device
+def attn_decode(q: torch.Tensor, kv_cache: torch.Tensor, n_keys=None, causal: bool = True, softmax_scale: float = None,
+                out: torch.Tensor = None, workspace: torch.Tensor = None) -> torch.Tensor:
+    """``attn_decode_fp8kv`` over a 16-bit cache (``mq_attn_decode``): kv_cache [capacity, 2 * kv_heads, 128] in q's dtype (K heads
+    then V heads, what ``kv_append_rope`` writes; the K|V columns of the fused q|k|v output work in place), no scales.  The kernel
+    and its arithmetic are the e4m3 one's with both scales 1: equal cache values give equal bits.  n_keys, causal, workspace: as
+    there."""
+    _need_cuda(q, kv_cache, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
+    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, None, n_keys, workspace, storage=q.dtype)
+    if out is None:
+        out = torch.empty((R, H * D), dtype=q.dtype, device=q.device)
+    assert out.dtype == q.dtype and out.shape == (R, H * D) and out.stride(1) == 1
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    call("mq_attn_decode", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
+         float(softmax_scale), 1 if causal else 0, out.data_ptr(), out.stride(0) if R > 1 else H * D, wptr, wbytes, _stream())
+    return out
+
+
+@_on_device
 def attn_decode_quant_i8(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.Tensor, scale0: float,
                          scale1: Optional[float] = None, *, n_keys=None, causal: bool = True, softmax_scale: float = None,
                          row_sel: Optional[torch.Tensor] = None, out=None, tiled: bool = False, workspace: torch.Tensor = None):
     """``attn_decode_fp8kv`` with the next Linear's static int8 quantizer fused into the final store
     (``mq_attn_decode_fp8kv_quant_i8``): returns the int8 activations ``quantize_act_i8`` would produce from the 16-bit decode
-    output of the same plan ([R, heads * 128] row-major, or a ``TiledAct``)."""
+    output of the same plan ([R, heads * 128] row-major, or a ``TiledAct``).  kv_scale = None with a cache of q's dtype: the same
+    over a 16-bit cache, ``attn_decode`` with the quantizer fused (``mq_attn_decode_quant_i8``)."""
     _need_cuda(q, kv_cache, kv_scale, row_sel, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
-    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace)
+    fp8 = kv_cache.dtype == torch.float8_e4m3fn and kv_scale is not None
+    assert fp8 or (kv_scale is None and kv_cache.dtype == q.dtype), \
+        f"kv_cache / kv_scale: a float8_e4m3fn cache with its kv_scale, or a cache of q's dtype ({q.dtype}) with kv_scale = None " \
+        f"(got {kv_cache.dtype}, kv_scale {'given' if kv_scale is not None else 'None'})"
+    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace, storage=kv_cache.dtype)
     out, optr, K_pad, ldo = _out_act(out, tiled, R, H * D, q.device)
     if softmax_scale is None:
         softmax_scale = D ** -0.5
+    if not fp8:
+        call("mq_attn_decode_quant_i8", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
+             float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo, wptr,
+             wbytes, _stream())
+        return out
     call("mq_attn_decode_fp8kv_quant_i8", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
          kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel),
          optr, K_pad, ldo, wptr, wbytes, _stream())
@@ -755,15 +788,31 @@ def kv_append_rope_fp8(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv
     token t = n - R + r and uses row clamp(t + rope_delta, 0, rows - 1) of cos / sin [rows, D] (qkv's dtype, contiguous);
     rope_delta: an int or an int32 CUDA tensor of one element (HF Qwen2-VL's ``rope_deltas``), default 0.  cos = sin = None: append
     only.  With both integers on the device a captured step replays while the cache grows.  Returns qkv."""
+    return _kv_append(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, torch.float8_e4m3fn)
+
+
+@_on_device
+def kv_append_rope(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, cos: torch.Tensor = None, sin: torch.Tensor = None,
+                   n_keys=None, rope_delta=None) -> torch.Tensor:
+    """``kv_append_rope_fp8`` into a 16-bit cache (``mq_kv_append_rope``): kv_cache [capacity, 2 * kv_heads, D] in qkv's dtype; rows
+    [n - R, n) receive the BITS of the rotated K columns and of the V columns -- nothing is quantised, there are no scales.  What
+    ``attn_decode`` reads next.  Every other argument as there.  Returns qkv."""
+    assert kv_cache.dtype == qkv.dtype, f"kv_cache must have qkv's dtype {qkv.dtype} (got {kv_cache.dtype}); an e4m3 cache: kv_append_rope_fp8"
+    return _kv_append(qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta, qkv.dtype)
+
+
+def _kv_append(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, storage):
+    """The two append entry points: the checks, the device integers and the call.  storage: the cache's dtype."""
     is_t = lambda v: v if isinstance(v, torch.Tensor) else None
     _need_cuda(qkv, kv_cache, kv_scale, cos, sin, is_t(n_keys), is_t(rope_delta))
     cap, H2, D = kv_cache.shape
-    assert H2 % 2 == 0 and kv_cache.dtype == torch.float8_e4m3fn and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
+    assert H2 % 2 == 0 and kv_cache.dtype == storage and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
     hkv = H2 // 2
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (heads + H2) * D, \
         f"qkv must be [R, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}] (got {tuple(qkv.shape)})"
     R = qkv.shape[0]
-    _check_kv_scale(kv_scale, hkv)
+    if kv_scale is not None:
+        _check_kv_scale(kv_scale, hkv)
     if isinstance(n_keys, torch.Tensor):
         T, n_dev = cap, _device_int(n_keys, "n_keys", qkv.device)
     else:
@@ -778,9 +827,12 @@ def kv_append_rope_fp8(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv
     if cos is None or (not isinstance(rope_delta, torch.Tensor) and not rope_delta):
         rope_delta = None                                              # no table, or a host-side 0: nothing to offset
     d_dev = _device_int(rope_delta, "rope_delta", qkv.device)
-    call("mq_kv_append_rope_fp8", qkv.data_ptr(), dtype_code(qkv.dtype), R, T, _ptr(n_dev), _ptr(d_dev), heads, hkv, D,
-         qkv.stride(0) if R > 1 else qkv.shape[1], _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(),
-         kv_cache.stride(0) if cap > 1 else H2 * D, kv_scale.data_ptr(), _stream())
+    args = (qkv.data_ptr(), dtype_code(qkv.dtype), R, T, _ptr(n_dev), _ptr(d_dev), heads, hkv, D, qkv.stride(0) if R > 1 else qkv.shape[1],
+            _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(), kv_cache.stride(0) if cap > 1 else H2 * D)
+    if storage == torch.float8_e4m3fn:
+        call("mq_kv_append_rope_fp8", *args, kv_scale.data_ptr(), _stream())
+    else:
+        call("mq_kv_append_rope", *args, _stream())
     return qkv
 
 

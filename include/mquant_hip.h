@@ -434,6 +434,43 @@ int mq_attn_decode_debug_force(int splits, int keys_per_split);
 #define MQ_ATTN_DECODE_PLAN_INTS 5
 int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads, int *plan);
 
+/* The four decode attention calls over a BATCH: B sequences (1 .. 65535) of R rows each in one pair of launches, so that a
+ * generation step streams the weights once for B tokens.  Sequence b is the second grid dimension of both launches and uses
+ *   - its own key count n_b = clamp(n_keys_dev[b], R, T) (n_keys_dev: [B] int32 on the device; NULL: every sequence has T keys),
+ *   - its own cache at kv_cache + b * seq_stride ELEMENTS of the storage (64-bit arithmetic; seq_stride >= T * ldkv, a multiple of
+ *     16 bytes).  The 32-bit offsets inside a cache stay per sequence: (T + 32) x the row stride < 4 GiB holds for ONE sequence,
+ *     the batch as a whole may be larger,
+ *   - rows [b R, (b + 1) R) of q, out and row_sel (q / out: [B * R][ld]; the fused int8 store addresses global row b R + r, also in
+ *     the tiled layout),
+ *   - its own slice of `workspace`, which holds at least mq_attn_decode_batch_workspace_bytes(B, R, T, heads, kv_heads) bytes.
+ * Everything inside a workgroup is the single-sequence kernel: a split at or beyond n_b leaves without writing and the merge does not
+ * read its slot; nothing at or beyond key n_b of sequence b reaches the output, whatever those cache rows hold.  The plan is that of
+ * the siblings with 2 x CUs / (kv_heads x B) key ranges wanted per sequence (B = 1: the sibling's plan, integer for integer);
+ * mq_attn_decode_debug_force applies.  The output bits of sequence b depend on its own q, cache and length and on (splits, keys per
+ * split) only: a batched call equals B single-sequence calls under the same plan, bit for bit.  B = 1 ignores seq_stride and IS the
+ * sibling.  Everything else -- dtypes, strides, alignment, causal, the quantizer -- as the siblings state it. */
+int mq_attn_decode_fp8kv_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                               int head_dim, long ldq, const uint8_t *kv_cache, long ldkv, long seq_stride, const float *kv_scale,
+                               float softmax_scale, int causal, void *out, long ldo, void *workspace, size_t workspace_bytes,
+                               void *stream);
+int mq_attn_decode_fp8kv_quant_i8_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads,
+                                        int kv_heads, int head_dim, long ldq, const uint8_t *kv_cache, long ldkv, long seq_stride,
+                                        const float *kv_scale, float softmax_scale, int causal, float scale0, float scale1,
+                                        const uint8_t *row_sel, int8_t *out, long K_pad, long ldo, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+int mq_attn_decode_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                         int head_dim, long ldq, const void *kv_cache, long ldkv, long seq_stride, float softmax_scale, int causal,
+                         void *out, long ldo, void *workspace, size_t workspace_bytes, void *stream);
+int mq_attn_decode_quant_i8_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                                  int head_dim, long ldq, const void *kv_cache, long ldkv, long seq_stride, float softmax_scale,
+                                  int causal, float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+/* The workspace of a batched call (B x the per-sequence figure of ITS plan) and its plan, in the MQ_ATTN_DECODE_PLAN_* slots: SPLITS,
+ * KEYS_PER_SPLIT and PASSES per sequence, GRID = all kv_heads x splits x B workgroups of the first launch, WORKSPACE for the whole
+ * batch.  Host arithmetic only, as the siblings. */
+size_t mq_attn_decode_batch_workspace_bytes(int B, int R, long T, int heads, int kv_heads);
+int mq_attn_decode_batch_debug_plan(int B, int R, long T, int heads, int kv_heads, int *plan);
+
 /* The launch in front of mq_attn_decode_fp8kv in a generation step: rotate Q and K of the R new rows (1 .. 8) in place and
  * quantise K|V into rows [n - R, n) of the e4m3 cache, at a position read from DEVICE memory -- with it a whole decode step is
  * captured once and advances by incrementing one int32 (no reference counterpart; checkers = mq_rope_inplace and mq_kv_quant_fp8).
@@ -464,6 +501,20 @@ int mq_kv_append_rope(void *qkv, int dtype, int R, long T, const int32_t *n_keys
                       int heads, int kv_heads, int head_dim, long ldqkv,
                       const void *cos, const void *sin, long table_rows,
                       void *kv_cache, long ldkv, void *stream);
+/* The two appends over a BATCH of B sequences (1 .. 65535) of R new rows each, in front of the batched decode attention: qkv is
+ * [B * R][ldqkv], rows [b R, (b + 1) R) belong to sequence b; n_b = clamp(n_keys_dev[b], R, T) and the offset rope_delta_dev[b] are
+ * per sequence (both [B] int32 on the device, either may be NULL as above: every sequence has its own image, hence its own offset);
+ * sequence b's cache starts at kv_cache + b * seq_stride elements (seq_stride >= T * ldkv, a multiple of 16 bytes; ignored at B = 1).
+ * Per sequence everything is the sibling: both clamps, the lane-to-element map, append-only mode, what is and is not written -- the
+ * bytes between the caches of two sequences included. */
+int mq_kv_append_rope_fp8_batch(void *qkv, int dtype, int B, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                                int heads, int kv_heads, int head_dim, long ldqkv,
+                                const void *cos, const void *sin, long table_rows,
+                                uint8_t *kv_cache, long ldkv, long seq_stride, const float *kv_scale, void *stream);
+int mq_kv_append_rope_batch(void *qkv, int dtype, int B, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                            int heads, int kv_heads, int head_dim, long ldqkv,
+                            const void *cos, const void *sin, long table_rows,
+                            void *kv_cache, long ldkv, long seq_stride, void *stream);
 
 /* out[m][n] = sum_k x[m][k] * W[n][k], 16-bit x ([M <= 8, K], ldx elements per row) and W ([N, K], ldw), fp32 products and sums,
  * one rounding to the same 16-bit dtype: the UNQUANTIZED lm_head on the last position(s) of a prefill (the reference leaves
@@ -499,6 +550,12 @@ size_t mq_gemv_argmax_workspace_bytes(int M, long N);
  * depends on R and dim only. */
 int mq_embed_gather(const void *table, int dtype, long vocab, long dim, long ldt, const int32_t *ids_dev, int R, void *out, long ldo,
                     int32_t *id_log, long log_rows, const int32_t *n_keys_dev, void *stream);
+/* The same launch for B = 1 .. 8 SEQUENCES of one new row each (the first launch of a batched generation step):
+ * out[b] = table[clamp(ids_dev[b], 0, vocab - 1)], and with id_log != NULL ([B][ld_log] int32, ld_log >= log_rows) the clamped id of
+ * sequence b is stored at id_log[b * ld_log + n_b - 1], n_b = n_keys_dev ? clamp(n_keys_dev[b], 1, log_rows) : log_rows
+ * (n_keys_dev: [B]).  Nothing else is written. */
+int mq_embed_gather_batch(const void *table, int dtype, long vocab, long dim, long ldt, const int32_t *ids_dev, int B, void *out,
+                          long ldo, int32_t *id_log, long ld_log, long log_rows, const int32_t *n_keys_dev, void *stream);
 
 
 /* ---------------------------------------------------------------------------

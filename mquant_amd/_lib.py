@@ -72,6 +72,17 @@ SIGNATURES = {
     "mq_attn_decode_debug_plan": (_i, [_i, _l, _i, _i, _vp]),
     "mq_kv_append_rope_fp8": (_i, [_vp, _i, _i, _l, _vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _vp, _l, _vp, _vp]),
     "mq_kv_append_rope": (_i, [_vp, _i, _i, _l, _vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _vp, _l, _vp]),
+    "mq_attn_decode_fp8kv_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _i, _i, _i, _l, _vp, _l, _l, _vp, _f, _i, _vp, _l, _vp, C.c_size_t, _vp]),
+    "mq_attn_decode_fp8kv_quant_i8_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _i, _i, _i, _l, _vp, _l, _l, _vp, _f, _i, _f, _f, _vp, _vp, _l, _l,
+                                                 _vp, C.c_size_t, _vp]),
+    "mq_attn_decode_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _i, _i, _i, _l, _vp, _l, _l, _f, _i, _vp, _l, _vp, C.c_size_t, _vp]),
+    "mq_attn_decode_quant_i8_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _i, _i, _i, _l, _vp, _l, _l, _f, _i, _f, _f, _vp, _vp, _l, _l, _vp,
+                                           C.c_size_t, _vp]),
+    "mq_attn_decode_batch_workspace_bytes": (C.c_size_t, [_i, _i, _l, _i, _i]),
+    "mq_attn_decode_batch_debug_plan": (_i, [_i, _i, _l, _i, _i, _vp]),
+    "mq_kv_append_rope_fp8_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _vp, _l, _l, _vp, _vp]),
+    "mq_kv_append_rope_batch": (_i, [_vp, _i, _i, _i, _l, _vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _vp, _l, _l, _vp]),
+    "mq_embed_gather_batch": (_i, [_vp, _i, _l, _l, _l, _vp, _i, _vp, _l, _vp, _l, _l, _vp, _vp]),
     "mq_gemv_f16": (_i, [_vp, _i, _i, _l, _l, _vp, _l, _l, _vp, _l, _vp]),
     "mq_gemv_f16_argmax": (_i, [_vp, _i, _i, _l, _l, _vp, _l, _l, _vp, _l, _vp, _vp, C.c_size_t, _vp]),
     "mq_gemv_argmax_workspace_bytes": (C.c_size_t, [_i, _l]),

@@ -46,6 +46,12 @@
 // loads per lane next to the eight K operands in use do not fit the 256 registers of two workgroups per CU, so the 16-bit path
 // prefetches the next block's K only (issued once S has consumed the operands, in flight during the softmax and P V) and
 // loads the CURRENT block's V at the top of the iteration, in flight during S -- its registers are then free for P V.
+//
+// A BATCH of B sequences (the *_batch entry points) is the second grid dimension of both launches: workgroup (x, b) is the
+// workgroup x of a single-sequence call on sequence b -- its own key count n_keys_dev[b], its own cache kv + b * seq_stride, the
+// rows [b R, (b + 1) R) of q / out / row_sel, its own slice of the workspace -- and everything inside it is the source above
+// (decode_sequence shifts the argument block; the single-sequence entry points launch B = 1, where every shift is zero).  The
+// plan fills the chip with kv_heads x B x splits workgroups; with ragged lengths a short sequence's empty splits leave at once.
 #include "attn_common.h"
 
 namespace mq {
@@ -60,12 +66,12 @@ constexpr int AD_STATS = AD_NW * 32 * 2 * 4;     // [wave][32 columns][m, l]
 constexpr int AD_PART = AD_D + 2;                // floats of one partial state: acc[128], then (m, l) in a table of their own
 
 struct AttnDecArgs {
-    const void *q;             // [R, heads * 128] (row stride ldq elements), fp16 / bf16
+    const void *q;             // [R, heads * 128] (row stride ldq elements), fp16 / bf16; a batch: [B * R, ..], as out, qout and row_sel
     const uint8_t *kv;         // cache: [T][ldkv] elements (e4m3 bytes, or q's dtype), per token the K heads, then the V heads
     const float *kv_scale;     // [2 * kv_heads]; null for a 16-bit cache (no scales: both factors 1)
-    const int32_t *n_dev;      // optional device-side key count
+    const int32_t *n_dev;      // optional device-side key count; a batch: [B]
     void *out;                 // [R, heads * 128] (row stride ldo elements), q's dtype
-    float *ws;                 // splits > 1: acc [splits][R * heads][128], then ml [splits][R * heads][2]
+    float *ws;                 // splits > 1: acc [splits][R * heads][128], then ml [splits][R * heads][2]; a batch: B such slices
     long T, ldq, ldkv, ldo;
     int R, heads, kv_heads, causal;
     int splits, kps, passes;
@@ -78,7 +84,24 @@ struct AttnDecArgs {
     const uint8_t *row_sel;
     float qi0, qi1;
     int qr0, qr1;
+    // a batch: the cache of sequence b starts seq_stride ELEMENTS after that of b - 1 (0 at B = 1); row0 is set by decode_sequence
+    long seq_stride, row0;
+    int B;
 };
+
+// Workgroup (x, b) of a batched launch becomes workgroup x of a call on sequence b alone: the key count, the cache and the
+// workspace slice move to b's, and row0 = b R is the global row of its first query row (q, out, row_sel and the tiled int8
+// layout are addressed by global row).  b is blockIdx.y: uniform, scalar arithmetic on the argument block.  KVB = bytes of a
+// cache element.
+template <int KVB>
+__device__ __forceinline__ void decode_sequence(AttnDecArgs &p)
+{
+    const long b = blockIdx.y;
+    p.row0 = b * p.R;
+    p.kv += b * p.seq_stride * KVB;
+    if (p.n_dev) p.n_dev += b;
+    if (p.ws) p.ws += b * ((long)p.splits * p.R * p.heads * AD_PART);
+}
 
 // n = clamp(*n_dev, R, T) through the VECTOR memory path (a buffer load; every lane receives the same dword)
 __device__ __forceinline__ long decode_key_count(const AttnDecArgs &p)
@@ -118,6 +141,7 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
     __shared__ __attribute__((aligned(16))) char smem[AD_NW * AD_WAVE_LDS + AD_STATS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    decode_sequence<KVB>(p);
     const int kvh = blockIdx.x % p.kv_heads, split = blockIdx.x / p.kv_heads;
     const int rep = p.heads / p.kv_heads, m_all = p.R * rep;
     const long n = decode_key_count(p);
@@ -169,11 +193,11 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
         const int col = lane & 31, m = pass * AD_M + col;
         const bool live = col < AD_M && m < m_all;
         const int row = live ? m / rep : 0, head = kvh * rep + (live ? m - row * rep : 0);
-        const unsigned sel = (live && p.qout && p.row_sel) ? p.row_sel[row] : 0;
+        const unsigned sel = (live && p.qout && p.row_sel) ? p.row_sel[p.row0 + row] : 0;
         const long kmax = p.causal ? n - p.R + row : n - 1;           // last key this row attends to
         v4i Qf[8];
         {
-            const unsigned short *qp = reinterpret_cast<const unsigned short *>(p.q) + row * p.ldq + (long)head * AD_D + 64 * ko;
+            const unsigned short *qp = reinterpret_cast<const unsigned short *>(p.q) + (p.row0 + row) * p.ldq + (long)head * AD_D + 64 * ko;
 #pragma unroll
             for (int ds = 0; ds < 8; ++ds) Qf[ds] = live ? *reinterpret_cast<const v4i *>(qp + ds * 8) : v4i{0, 0, 0, 0};
         }
@@ -328,7 +352,7 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const float v4[4] = {acc[4 * g] * f, acc[4 * g + 1] * f, acc[4 * g + 2] * f, acc[4 * g + 3] * f};
-                    decode_store4<DT>(p, row, c0 + 8 * g, v4, sel);
+                    decode_store4<DT>(p, p.row0 + row, c0 + 8 * g, v4, sel);
                 }
             } else {
                 const long rows = (long)p.R * p.heads, slot = (long)split * rows + (long)row * p.heads + head;
@@ -350,6 +374,7 @@ __global__ __launch_bounds__(AD_NW * 64, 2) void attn_decode_kernel(AttnDecArgs 
 template <int DT>
 __global__ __launch_bounds__(256) void attn_decode_merge_kernel(AttnDecArgs p)
 {
+    decode_sequence<0>(p);                                            // the merge never touches the cache: its shift is unused
     const long rows = (long)p.R * p.heads, slot = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
     if (slot >= rows) return;
     const int d = 4 * (threadIdx.x & 31);
@@ -371,9 +396,9 @@ __global__ __launch_bounds__(256) void attn_decode_merge_kernel(AttnDecArgs p)
         for (int e = 0; e < 4; ++e) acc[e] += a[e] * w;
     }
     const float f = L > 0.0f ? s_v / L : 0.0f;
-    const unsigned sel = (p.qout && p.row_sel) ? p.row_sel[row] : 0;
+    const unsigned sel = (p.qout && p.row_sel) ? p.row_sel[p.row0 + row] : 0;
     const float v4[4] = {acc[0] * f, acc[1] * f, acc[2] * f, acc[3] * f};
-    decode_store4<DT>(p, row, (long)head * AD_D + d, v4, sel);
+    decode_store4<DT>(p, p.row0 + row, (long)head * AD_D + d, v4, sel);
 }
 
 struct AttnDecPlan {
@@ -386,12 +411,14 @@ struct AttnDecPlan {
 static thread_local int g_dec_splits = 0, g_dec_kps = 0;      // TEST-ONLY (mq_attn_decode_debug_force): 0 = the heuristic
 
 // Everything the host decides for a call; the launch, the workspace query and mq_attn_decode_debug_plan all come here.
-// Heuristic: two workgroups fit a CU (LDS), so 2 x CUs / kv_heads splits fill the chip; a split is never shorter than 128 keys
-// -- one block for each of the workgroup's four waves: below that the critical path (one block) no longer shrinks and only
-// the merge grows.
-static int attn_decode_plan(const char *who, int R, long T, int heads, int kv_heads, int cus, mq::AttnDecPlan &pl)
+// Heuristic: two workgroups fit a CU (LDS), so 2 x CUs / (kv_heads x B) splits per sequence fill the chip; a split is never
+// shorter than 128 keys -- one block for each of the workgroup's four waves: below that the critical path (one block) no longer
+// shrinks and only the merge grows.  B enters nowhere else: splits and keys_per_split are per sequence, grid and ws_bytes are
+// B times the single-sequence figures, and B = 1 is the single-sequence plan integer for integer.
+static int attn_decode_plan(const char *who, int B, int R, long T, int heads, int kv_heads, int cus, mq::AttnDecPlan &pl)
 {
     using namespace mq;
+    MQ_REQUIRE(B >= 1 && B <= 65535, "%s: B = %d sequences (1 .. 65535: the second grid dimension)", who, B);
     MQ_REQUIRE(R >= 1 && R <= 8, "%s: R = %d query rows (1 .. 8)", who, R);
     MQ_REQUIRE(heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0, "%s: bad head counts %d / %d", who, heads, kv_heads);
     MQ_REQUIRE(T >= R, "%s: T = %ld keys for R = %d rows (the rows are the last R positions: T >= R)", who, T, R);
@@ -405,7 +432,7 @@ static int attn_decode_plan(const char *who, int R, long T, int heads, int kv_he
         splits = g_dec_splits;
         kps = ceil_div(ceil_div(T, splits), AD_KB) * AD_KB;
     } else {
-        const long want = 2L * cus / kv_heads > 1 ? 2L * cus / kv_heads : 1;
+        const long per = (long)kv_heads * B, want = 2L * cus / per > 1 ? 2L * cus / per : 1;
         kps = ceil_div(ceil_div(T, want), AD_KB) * AD_KB;
         if (kps < AD_NW * AD_KB) kps = AD_NW * AD_KB;
         splits = ceil_div(T, kps);
@@ -413,11 +440,13 @@ static int attn_decode_plan(const char *who, int R, long T, int heads, int kv_he
     MQ_REQUIRE(splits * kps >= T && T > (splits - 1) * kps, "%s: forced plan of %ld splits of %ld keys does not cut T = %ld keys into non-empty ranges",
                who, splits, kps, T);
     MQ_REQUIRE(splits * kv_heads < (1L << 31), "%s: %ld splits of %d kv heads exceed the grid", who, splits, kv_heads);
+    MQ_REQUIRE(splits * kv_heads * B < (1L << 31) && (long)B * R * heads < (1L << 31),
+               "%s: B = %d sequences of %ld splits x %d kv heads, or of %d x %d (row, head) pairs, do not fit an int", who, B, splits, kv_heads, R, heads);
     pl.splits = (int)splits;
     pl.kps = (int)kps;
-    pl.grid = (int)(splits * kv_heads);
+    pl.grid = (int)(splits * kv_heads * B);
     pl.passes = (R * (heads / kv_heads) + AD_M - 1) / AD_M;
-    pl.ws_bytes = splits > 1 ? (size_t)splits * R * heads * AD_PART * sizeof(float) : 0;
+    pl.ws_bytes = splits > 1 ? (size_t)B * splits * R * heads * AD_PART * sizeof(float) : 0;
     return MQ_OK;
 }
 
@@ -429,13 +458,13 @@ extern "C" int mq_attn_decode_debug_force(int splits, int keys_per_split)
     return MQ_OK;
 }
 
-extern "C" int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads, int *plan)
+static int attn_decode_debug_plan(const char *who, int B, int R, long T, int heads, int kv_heads, int *plan)
 {
-    MQ_REQUIRE(plan, "mq_attn_decode_debug_plan: null pointer");
+    MQ_REQUIRE(plan, "%s: null pointer", who);
     mq::AttnDecPlan pl;
-    const int rc = attn_decode_plan("mq_attn_decode_debug_plan", R, T, heads, kv_heads, mq::device_cu_count(), pl);
+    const int rc = attn_decode_plan(who, B, R, T, heads, kv_heads, mq::device_cu_count(), pl);
     if (rc != MQ_OK) return rc;
-    MQ_REQUIRE(pl.ws_bytes < (1UL << 31), "mq_attn_decode_debug_plan: workspace of %zu bytes does not fit the plan's int", pl.ws_bytes);
+    MQ_REQUIRE(pl.ws_bytes < (1UL << 31), "%s: workspace of %zu bytes does not fit the plan's int", who, pl.ws_bytes);
     plan[MQ_ATTN_DECODE_PLAN_SPLITS] = pl.splits;
     plan[MQ_ATTN_DECODE_PLAN_KEYS_PER_SPLIT] = pl.kps;
     plan[MQ_ATTN_DECODE_PLAN_GRID] = pl.grid;
@@ -444,10 +473,27 @@ extern "C" int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads,
     return MQ_OK;
 }
 
+extern "C" int mq_attn_decode_debug_plan(int R, long T, int heads, int kv_heads, int *plan)
+{
+    return attn_decode_debug_plan("mq_attn_decode_debug_plan", 1, R, T, heads, kv_heads, plan);
+}
+
+extern "C" int mq_attn_decode_batch_debug_plan(int B, int R, long T, int heads, int kv_heads, int *plan)
+{
+    return attn_decode_debug_plan("mq_attn_decode_batch_debug_plan", B, R, T, heads, kv_heads, plan);
+}
+
 extern "C" size_t mq_attn_decode_workspace_bytes(int R, long T, int heads, int kv_heads)
 {
     mq::AttnDecPlan pl;
-    if (attn_decode_plan("mq_attn_decode_workspace_bytes", R, T, heads, kv_heads, mq::device_cu_count(), pl) != MQ_OK) return 0;
+    if (attn_decode_plan("mq_attn_decode_workspace_bytes", 1, R, T, heads, kv_heads, mq::device_cu_count(), pl) != MQ_OK) return 0;
+    return pl.ws_bytes;
+}
+
+extern "C" size_t mq_attn_decode_batch_workspace_bytes(int B, int R, long T, int heads, int kv_heads)
+{
+    mq::AttnDecPlan pl;
+    if (attn_decode_plan("mq_attn_decode_batch_workspace_bytes", B, R, T, heads, kv_heads, mq::device_cu_count(), pl) != MQ_OK) return 0;
     return pl.ws_bytes;
 }
 
@@ -462,7 +508,7 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int kvb, int dty
     // the running maximum is taken over RAW scores and the (positive) scale applied afterwards (attn_prefill.hip)
     MQ_REQUIRE(a.softmax_scale > 0.0f && a.softmax_scale < 3.0e38f, "%s: softmax_scale must be positive and finite (got %g)", who, (double)a.softmax_scale);
     AttnDecPlan pl;
-    const int rc = attn_decode_plan(who, a.R, a.T, a.heads, a.kv_heads, device_cu_count(), pl);
+    const int rc = attn_decode_plan(who, a.B, a.R, a.T, a.heads, a.kv_heads, device_cu_count(), pl);
     if (rc != MQ_OK) return rc;
     MQ_REQUIRE(a.q && a.kv && (a.kv_scale || kvb == 2) && (a.out || a.qout), "%s: null pointer", who);
     MQ_REQUIRE(a.ldq >= (long)a.heads * D && a.ldkv >= 2L * a.kv_heads * D && (a.qout || a.ldo >= (long)a.heads * D), "%s: row strides too short", who);
@@ -473,6 +519,13 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int kvb, int dty
     // K / V are addressed through 32-bit buffer offsets (one block past the last row included)
     MQ_REQUIRE(a.ldkv < (1L << 32) && (a.T + AD_KB) * a.ldkv * kvb < (1L << 32),
                "%s: (T + 32) x the cache row stride in bytes must stay below 4 GiB (T %ld, stride %ld bytes)", who, a.T, a.ldkv * kvb);
+    if (a.B > 1) {                                                    // sequence b's cache: kv + b * seq_stride (64-bit), rows as above
+        MQ_REQUIRE(a.seq_stride >= a.T * a.ldkv, "%s: seq_stride %ld shorter than one sequence's T * ldkv = %ld elements", who, a.seq_stride,
+                   a.T * a.ldkv);
+        MQ_REQUIRE((a.seq_stride * kvb) % 16 == 0, "%s: seq_stride must be a multiple of 16 bytes (got %ld bytes)", who, a.seq_stride * kvb);
+    } else {
+        a.seq_stride = 0;
+    }
     if (pl.ws_bytes) {
         MQ_REQUIRE(workspace && workspace_bytes >= pl.ws_bytes, "%s: %d key splits need a workspace of %zu bytes (got %zu)", who, pl.splits, pl.ws_bytes,
                    workspace ? workspace_bytes : (size_t)0);
@@ -483,7 +536,7 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int kvb, int dty
     a.kps = pl.kps;
     a.passes = pl.passes;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)pl.grid), block(AD_NW * 64);
+    const dim3 grid((unsigned)(pl.grid / a.B), (unsigned)a.B), block(AD_NW * 64);
     if (kvb == 1) {
         if (dtype == MQ_F16) hipLaunchKernelGGL((attn_decode_kernel<MQ_F16, 1>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((attn_decode_kernel<MQ_BF16, 1>), grid, block, 0, st, a);
@@ -493,7 +546,7 @@ static int attn_decode_run(const char *who, mq::AttnDecArgs &a, int kvb, int dty
     }
     int lrc = check_launch("attn_decode");
     if (lrc != MQ_OK || pl.splits == 1) return lrc;
-    const dim3 mgrid((unsigned)((a.R * a.heads + 7) / 8));
+    const dim3 mgrid((unsigned)((a.R * a.heads + 7) / 8), (unsigned)a.B);
     if (dtype == MQ_F16) hipLaunchKernelGGL(attn_decode_merge_kernel<MQ_F16>, mgrid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(attn_decode_merge_kernel<MQ_BF16>, mgrid, dim3(256), 0, st, a);
     return check_launch("attn_decode_merge");
@@ -507,6 +560,7 @@ static mq::AttnDecArgs attn_decode_args(const void *q, int R, long T, const int3
     a.q = q; a.kv = reinterpret_cast<const uint8_t *>(kv_cache); a.kv_scale = kv_scale; a.n_dev = n_keys_dev; a.out = out; a.T = T; a.ldq = ldq;
     a.ldkv = ldkv; a.ldo = ldo; a.R = R; a.heads = heads; a.kv_heads = kv_heads; a.causal = causal ? 1 : 0; a.softmax_scale = softmax_scale;
     a.qs0 = a.qs1 = a.qi0 = a.qi1 = 1.0f;
+    a.B = 1;
     return a;
 }
 
@@ -557,6 +611,58 @@ extern "C" int mq_attn_decode_quant_i8(const void *q, int dtype, int R, long T, 
 {
     const char *who = "mq_attn_decode_quant_i8";
     mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, nullptr, softmax_scale, causal, nullptr, 0);
+    const int rc = attn_decode_quant_args(who, a, scale0, scale1, row_sel, out, K_pad, ldo);
+    return rc != MQ_OK ? rc : attn_decode_run(who, a, 2, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+// ---- the four calls over a batch: B sequences of R rows each, sequence b's cache at kv_cache + b * seq_stride elements, its key
+// count at n_keys_dev[b].  B = 1 is the sibling (seq_stride is ignored).
+static void attn_decode_batch(mq::AttnDecArgs &a, int B, long seq_stride)
+{
+    a.B = B;
+    a.seq_stride = seq_stride;
+}
+
+extern "C" int mq_attn_decode_fp8kv_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                                          int head_dim, long ldq, const uint8_t *kv_cache, long ldkv, long seq_stride, const float *kv_scale,
+                                          float softmax_scale, int causal, void *out, long ldo, void *workspace, size_t workspace_bytes,
+                                          void *stream)
+{
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, kv_scale, softmax_scale, causal, out, ldo);
+    attn_decode_batch(a, B, seq_stride);
+    return attn_decode_run("mq_attn_decode_fp8kv_batch", a, 1, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_attn_decode_fp8kv_quant_i8_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads,
+                                                   int kv_heads, int head_dim, long ldq, const uint8_t *kv_cache, long ldkv, long seq_stride,
+                                                   const float *kv_scale, float softmax_scale, int causal, float scale0, float scale1,
+                                                   const uint8_t *row_sel, int8_t *out, long K_pad, long ldo, void *workspace,
+                                                   size_t workspace_bytes, void *stream)
+{
+    const char *who = "mq_attn_decode_fp8kv_quant_i8_batch";
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, kv_scale, softmax_scale, causal, nullptr, 0);
+    attn_decode_batch(a, B, seq_stride);
+    const int rc = attn_decode_quant_args(who, a, scale0, scale1, row_sel, out, K_pad, ldo);
+    return rc != MQ_OK ? rc : attn_decode_run(who, a, 1, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_attn_decode_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                                    int head_dim, long ldq, const void *kv_cache, long ldkv, long seq_stride, float softmax_scale, int causal,
+                                    void *out, long ldo, void *workspace, size_t workspace_bytes, void *stream)
+{
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, nullptr, softmax_scale, causal, out, ldo);
+    attn_decode_batch(a, B, seq_stride);
+    return attn_decode_run("mq_attn_decode_batch", a, 2, dtype, head_dim, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_attn_decode_quant_i8_batch(const void *q, int dtype, int B, int R, long T, const int32_t *n_keys_dev, int heads, int kv_heads,
+                                             int head_dim, long ldq, const void *kv_cache, long ldkv, long seq_stride, float softmax_scale,
+                                             int causal, float scale0, float scale1, const uint8_t *row_sel, int8_t *out, long K_pad, long ldo,
+                                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "mq_attn_decode_quant_i8_batch";
+    mq::AttnDecArgs a = attn_decode_args(q, R, T, n_keys_dev, heads, kv_heads, ldq, kv_cache, ldkv, nullptr, softmax_scale, causal, nullptr, 0);
+    attn_decode_batch(a, B, seq_stride);
     const int rc = attn_decode_quant_args(who, a, scale0, scale1, row_sel, out, K_pad, ldo);
     return rc != MQ_OK ? rc : attn_decode_run(who, a, 2, dtype, head_dim, workspace, workspace_bytes, stream);
 }

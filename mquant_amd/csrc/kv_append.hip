@@ -26,6 +26,11 @@
 // reads): the store is the kernel's second template parameter KVB, the bytes of a cache element.  With KVB = 2 nothing is
 // quantised -- cache row t receives the BITS of the rotated, rounded K heads and of the V heads -- and the lane-to-element map
 // is the same: a K lane stores its two 16-byte pieces, a V lane its two.
+//
+// A BATCH of B sequences (mq_kv_append_rope_fp8_batch, mq_kv_append_rope_batch) is the second grid dimension: workgroup (x, b) is
+// workgroup x of a single-sequence call on sequence b -- n from n_keys_dev[b], the offset from rope_delta_dev[b] (every sequence
+// has its own image, hence its own offset), the qkv rows [b R, (b + 1) R) and the cache at kv + b * seq_stride.  The
+// single-sequence entry points launch B = 1.
 #include "kv_rope_common.h"
 
 namespace mq {
@@ -39,6 +44,7 @@ struct KvAppendArgs {
     const int32_t *delta_dev;  // optional device-side RoPE position offset
     long T, ldqkv, ldkv, table_rows;
     int R, heads, kv_heads, head_dim;
+    long seq_stride;           // a batch: elements between the caches of consecutive sequences (0 at B = 1)
 };
 
 template <int DT>
@@ -64,13 +70,14 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
 {
     kernarg_warm<sizeof(KvAppendArgs)>();
     typedef typename Elem<DT>::T E;
+    const long b = blockIdx.y;                                        // the sequence of a batch (0 in a single-sequence call)
     long n = p.T, delta = 0;
     if (p.n_dev) {
-        n = load_device_int(p.n_dev);
+        n = load_device_int(p.n_dev + b);
         n = n < p.R ? p.R : n;                                       // memory safety: rows [n - R, n) lie inside [0, T)
         n = n > p.T ? p.T : n;
     }
-    if (p.delta_dev) delta = load_device_int(p.delta_dev);
+    if (p.delta_dev) delta = load_device_int(p.delta_dev + b);
 
     const unsigned gph = (unsigned)p.head_dim / 16;                   // lanes per head
     const unsigned per_row = (unsigned)(p.heads + 2 * p.kv_heads) * gph;
@@ -80,8 +87,8 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
     const unsigned hh = j / gph, g = j - hh * gph;                    // head of the row (Q, K, V in this order), lane of the head
     const long t = n - p.R + r;
     const int D = p.head_dim, half = D / 2, qk = p.heads + p.kv_heads;
-    E *row = reinterpret_cast<E *>(p.qkv) + (long)r * p.ldqkv;
-    uint8_t *crow = p.kv + t * p.ldkv * KVB;
+    E *row = reinterpret_cast<E *>(p.qkv) + (b * p.R + r) * p.ldqkv;
+    uint8_t *crow = p.kv + (b * p.seq_stride + t * p.ldkv) * KVB;
 
     if ((int)hh >= qk) {                                              // ---- V: sixteen consecutive elements, stored as they are
         const int vh = p.kv_heads + ((int)hh - qk);                   // head of the cache row
@@ -123,11 +130,12 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(KvAppendArgs p)
 }  // namespace mq
 
 // the checks and the launch of both entry points; kvb = bytes of a cache element: 1 = e4m3 with scales, 2 = qkv's dtype without
-static int kv_append_run(const char *who, const char *kernel, int kvb, void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev,
+static int kv_append_run(const char *who, const char *kernel, int kvb, void *qkv, int dtype, int B, int R, long T, const int32_t *n_keys_dev,
                          const int32_t *rope_delta_dev, int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin,
-                         long table_rows, void *kv_cache, long ldkv, const float *kv_scale, void *stream)
+                         long table_rows, void *kv_cache, long ldkv, long seq_stride, const float *kv_scale, void *stream)
 {
     using namespace mq;
+    MQ_REQUIRE(B >= 1 && B <= 65535, "%s: B = %d sequences (1 .. 65535: the second grid dimension)", who, B);
     MQ_REQUIRE(qkv && kv_cache && (kv_scale || kvb == 2), "%s: null pointer", who);
     MQ_REQUIRE(dtype == MQ_F16 || dtype == MQ_BF16, "%s: qkv dtype must be fp16 or bf16 (got %d)", who, dtype);
     MQ_REQUIRE(R >= 1 && R <= 8, "%s: R = %d new rows (1 .. 8)", who, R);
@@ -149,10 +157,17 @@ static int kv_append_run(const char *who, const char *kernel, int kvb, void *qkv
     MQ_REQUIRE(((uintptr_t)n_keys_dev) % 4 == 0, "%s: n_keys_dev must be 4-byte aligned", who);
     MQ_REQUIRE(((uintptr_t)rope_delta_dev) % 4 == 0, "%s: rope_delta_dev must be 4-byte aligned", who);
 
+    if (B > 1) {                                                      // sequence b's cache: kv_cache + b * seq_stride (64-bit)
+        MQ_REQUIRE(seq_stride >= T * ldkv, "%s: seq_stride %ld shorter than one sequence's T * ldkv = %ld elements", who, seq_stride, T * ldkv);
+        MQ_REQUIRE((seq_stride * kvb) % 16 == 0, "%s: seq_stride must be a multiple of 16 bytes (got %ld bytes)", who, seq_stride * kvb);
+    } else {
+        seq_stride = 0;
+    }
+
     KvAppendArgs a{qkv, cos, sin, reinterpret_cast<uint8_t *>(kv_cache), kv_scale, n_keys_dev, rope_delta_dev, T, ldqkv, ldkv, table_rows, R, heads, kv_heads,
-                   head_dim};
+                   head_dim, seq_stride};
     const unsigned lanes = (unsigned)(R * (cols / 16));
-    const dim3 grid((lanes + 255) / 256);
+    const dim3 grid((lanes + 255) / 256, (unsigned)B);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (kvb == 1) {
         if (dtype == MQ_F16) hipLaunchKernelGGL((kv_append_rope_kernel<MQ_F16, 1>), grid, dim3(256), 0, st, a);
@@ -168,14 +183,32 @@ extern "C" int mq_kv_append_rope_fp8(void *qkv, int dtype, int R, long T, const 
                                      int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
                                      uint8_t *kv_cache, long ldkv, const float *kv_scale, void *stream)
 {
-    return kv_append_run("mq_kv_append_rope_fp8", "kv_append_rope_fp8", 1, qkv, dtype, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv,
-                         cos, sin, table_rows, kv_cache, ldkv, kv_scale, stream);
+    return kv_append_run("mq_kv_append_rope_fp8", "kv_append_rope_fp8", 1, qkv, dtype, 1, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv,
+                         cos, sin, table_rows, kv_cache, ldkv, 0, kv_scale, stream);
 }
 
 extern "C" int mq_kv_append_rope(void *qkv, int dtype, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev, int heads,
                                  int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows, void *kv_cache,
                                  long ldkv, void *stream)
 {
-    return kv_append_run("mq_kv_append_rope", "kv_append_rope", 2, qkv, dtype, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv, cos, sin,
-                         table_rows, kv_cache, ldkv, nullptr, stream);
+    return kv_append_run("mq_kv_append_rope", "kv_append_rope", 2, qkv, dtype, 1, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim, ldqkv, cos, sin,
+                         table_rows, kv_cache, ldkv, 0, nullptr, stream);
+}
+
+// ---- the same two launches over a batch: B sequences of R rows each (qkv [B * R][ldqkv]), sequence b's cache at kv_cache +
+// b * seq_stride elements, its key count at n_keys_dev[b], its offset at rope_delta_dev[b].  B = 1 is the sibling.
+extern "C" int mq_kv_append_rope_fp8_batch(void *qkv, int dtype, int B, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                                           int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
+                                           uint8_t *kv_cache, long ldkv, long seq_stride, const float *kv_scale, void *stream)
+{
+    return kv_append_run("mq_kv_append_rope_fp8_batch", "kv_append_rope_fp8_batch", 1, qkv, dtype, B, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads,
+                         head_dim, ldqkv, cos, sin, table_rows, kv_cache, ldkv, seq_stride, kv_scale, stream);
+}
+
+extern "C" int mq_kv_append_rope_batch(void *qkv, int dtype, int B, int R, long T, const int32_t *n_keys_dev, const int32_t *rope_delta_dev,
+                                       int heads, int kv_heads, int head_dim, long ldqkv, const void *cos, const void *sin, long table_rows,
+                                       void *kv_cache, long ldkv, long seq_stride, void *stream)
+{
+    return kv_append_run("mq_kv_append_rope_batch", "kv_append_rope_batch", 2, qkv, dtype, B, R, T, n_keys_dev, rope_delta_dev, heads, kv_heads, head_dim,
+                         ldqkv, cos, sin, table_rows, kv_cache, ldkv, seq_stride, nullptr, stream);
 }

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .kv_cache import Fp8KVCache, KVCache16
+from .kv_cache import Fp8KVCache, Fp8KVCacheBatch, KVCache16, KVCache16Batch
 
 
 class GreedyLoop:
@@ -88,3 +88,82 @@ class GreedyLoop:
             run()
         first, self.pos = self.pos, self.pos + n
         return self.ids[first:first + n].cpu()
+
+
+class GreedyLoopBatch:
+    """``GreedyLoop`` for B <= 8 sequences that step together over a batched cache: one weight pass of the body and of lm_head
+    serves B tokens.  ``token`` [B], ``ids`` [B, capacity] (ids[b, t] = the id sequence b embedded at its cache position t) and
+    ``hidden`` [B, dim] live on the device; the step is
+
+        cache.advance(1)                                          # every n_keys[b] += 1
+        hidden[b] = embed_tokens[token[b]]; ids[b, n_keys[b] - 1] = token[b]      # ops.embed_gather_batch
+        h = rms_norm(body(hidden))                                # body: [B, dim] -> [B, dim]; it calls the batched cache's step
+        token = argmax(h @ lm_head.t())                           # ops.gemv_f16_argmax at M = B
+
+    All sequences step together: no stop ids, no per-sequence masks, no sampling."""
+
+    def __init__(self, cache: Union[Fp8KVCacheBatch, KVCache16Batch], embed_tokens: torch.Tensor, lm_head: torch.Tensor,
+                 body: Callable[[torch.Tensor], torch.Tensor], eps: float = 1e-6):
+        assert embed_tokens.dim() == 2 and lm_head.dim() == 2 and embed_tokens.shape[1] == lm_head.shape[1]
+        assert embed_tokens.dtype == lm_head.dtype == cache.dtype and embed_tokens.device == lm_head.device == cache.n_keys.device
+        assert 1 <= cache.batch <= 8, f"a batch of {cache.batch} sequences (1 .. 8: the rows of ops.embed_gather_batch and ops.gemv_f16_argmax)"
+        self.cache, self.embed_tokens, self.lm_head, self.body, self.eps = cache, embed_tokens, lm_head, body, eps
+        self.batch, self.dim = cache.batch, embed_tokens.shape[1]
+        dev = embed_tokens.device
+        self.token = torch.zeros((self.batch,), dtype=torch.int32, device=dev)                    # the ids the next step embeds
+        self.ids = torch.zeros((self.batch, cache.capacity), dtype=torch.int32, device=dev)
+        self.hidden = torch.empty((self.batch, self.dim), dtype=embed_tokens.dtype, device=dev)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.pos = [0] * self.batch  # host side: every sequence's cache position of the next step
+
+    def start(self, prompt_lens, first_tokens) -> None:
+        """The prefill wrote rows [0, prompt_lens[b]) of sequence b's caches and picked first_tokens[b]."""
+        prompt_lens, first_tokens = [int(n) for n in prompt_lens], [int(t) for t in first_tokens]
+        assert len(prompt_lens) == len(first_tokens) == self.batch, f"{self.batch} sequences need {self.batch} prompt lengths and first tokens"
+        assert all(0 <= n < self.cache.capacity for n in prompt_lens), \
+            f"prompt_lens {prompt_lens} leave no room in caches of {self.cache.capacity} rows"
+        self.cache.set_length(prompt_lens)
+        self.token.copy_(torch.tensor(first_tokens, dtype=torch.int32))
+        self.pos = prompt_lens
+
+    def step(self) -> None:
+        """One position of every sequence, on the current stream: capturable.  Does not move ``pos``."""
+        self.cache.advance(1)
+        ops.embed_gather_batch(self.embed_tokens, self.token, out=self.hidden, id_log=self.ids, n_keys=self.cache.n_keys)
+        h = self.body(self.hidden)
+        h = F.rms_norm(h, (self.dim,), eps=self.eps)
+        ops.gemv_f16_argmax(h, self.lm_head, token_out=self.token)
+
+    def capture(self) -> None:
+        """``GreedyLoop.capture`` per sequence: warm up, restore everything the warm-up step wrote -- ``n_keys``, ``token`` and, for
+        every sequence, the cache row and the log entry of its own position -- then capture ``step`` once."""
+        n_keys, token = self.cache.n_keys.clone(), self.token.clone()
+        at = [min(max(n + 1, 1), self.cache.capacity) - 1 for n in n_keys.cpu().tolist()]     # the positions the kernels' clamps give
+        seqs = list(range(self.batch))
+        rows, logged = [c.view(torch.uint8)[seqs, at] for c in self.cache.caches], self.ids[seqs, at]     # copies (indexed by lists)
+        side = torch.cuda.Stream(device=self.token.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self.step()
+        torch.cuda.current_stream().wait_stream(side)
+        self.cache.n_keys.copy_(n_keys)
+        self.token.copy_(token)
+        self.ids[seqs, at] = logged
+        for c, row in zip(self.cache.caches, rows):
+            c.view(torch.uint8)[seqs, at] = row
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            self.step()
+        self.graph = graph
+
+    def generate(self, n: int) -> torch.Tensor:
+        """n more positions of every sequence -> int32 CPU [B, n]: row b holds the ids embedded at positions pos_b .. pos_b + n - 1
+        (after ``start`` column 0 is first_tokens); the n-th generated ids are left in ``token``.  The copy is the only synchronisation."""
+        assert n >= 0 and max(self.pos) + n <= self.cache.capacity, \
+            f"{n} steps from positions {self.pos} exceed the cache's {self.cache.capacity} rows"
+        run = self.graph.replay if self.graph is not None else self.step
+        for _ in range(n):
+            run()
+        first, self.pos = self.pos, [p + n for p in self.pos]
+        ids = self.ids.cpu()
+        return torch.stack([ids[b, first[b]:first[b] + n] for b in range(self.batch)])

@@ -768,6 +768,194 @@ def attn_decode_quant_i8(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torc
     return out
 
 
+def attn_decode_batch_workspace_bytes(B: int, R: int, T: int, heads: int, kv_heads: int) -> int:
+    """Bytes of workspace a batched decode attention call needs (``mq_attn_decode_batch_workspace_bytes``).  Host arithmetic only."""
+    return int(_lib.load().mq_attn_decode_batch_workspace_bytes(B, R, T, heads, kv_heads))
+
+
+def attn_decode_batch_plan(B: int, R: int, T: int, heads: int, kv_heads: int) -> dict:
+    """``attn_decode_plan`` of a batched call (``mq_attn_decode_batch_debug_plan``): splits, keys_per_split and passes per sequence,
+    grid and workspace_bytes for the whole batch."""
+    import ctypes
+    plan = (ctypes.c_int * 5)()
+    call("mq_attn_decode_batch_debug_plan", B, R, T, heads, kv_heads, ctypes.cast(plan, ctypes.c_void_p))
+    return dict(zip(("splits", "keys_per_split", "grid", "passes", "workspace_bytes"), plan))
+
+
+def _batch_counts(v, B: int, name: str) -> Optional[torch.Tensor]:
+    """A per-sequence device integer of a batched call: None, or an int32 CUDA tensor of B elements (contiguous)."""
+    assert v is None or (isinstance(v, torch.Tensor) and v.dtype == torch.int32 and v.is_cuda and v.numel() == B and v.is_contiguous()), \
+        f"{name}: None or a contiguous int32 CUDA tensor of B = {B} elements"
+    return v
+
+
+def _batch_cache(kv_cache, storage):
+    """(B, capacity, 2 kv_heads, D, ldkv, seq_stride) of a batched cache [B, capacity, 2 * kv_heads, D]; strides in elements"""
+    B, cap, H2, D = kv_cache.shape
+    assert H2 % 2 == 0 and kv_cache.dtype == storage and kv_cache.stride(3) == 1 and kv_cache.stride(2) == D
+    ldkv = kv_cache.stride(1) if cap > 1 else H2 * D
+    return B, cap, H2, D, ldkv, kv_cache.stride(0) if B > 1 else cap * ldkv
+
+
+def _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, storage):
+    """``_decode_args`` of the batched entry points: (B, R, T, n_keys_dev, heads, kv_heads, D, ldq, ldkv, seq_stride, workspace ptr,
+    bytes).  q [B, R, heads, D]: the rows of a sequence ldq apart, the sequences R * ldq apart (a view of [B * R, ...])."""
+    B, R, H, D = q.shape
+    B2, cap, H2, D2, ldkv, seq_stride = _batch_cache(kv_cache, storage)
+    assert B2 == B and D2 == D and q.stride(3) == 1 and q.stride(2) == D
+    ldq = q.stride(1) if R > 1 else (q.stride(0) if B > 1 else H * D)
+    assert B == 1 or q.stride(0) == R * ldq, "q: the B * R rows must be one row stride apart (a view of a [B * R, ...] tensor)"
+    hkv = H2 // 2
+    if storage == torch.float8_e4m3fn:
+        _check_kv_scale(kv_scale, hkv)
+    else:
+        assert kv_scale is None and storage == q.dtype
+    n_dev = _batch_counts(n_keys, B, "n_keys")
+    need = attn_decode_batch_workspace_bytes(B, R, cap, H, hkv)
+    if workspace is None and need:
+        workspace = _decode_workspace(q.device, need)
+    wptr, wbytes = (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
+    return (B, R, cap, _ptr(n_dev), H, hkv, D, ldq, ldkv, seq_stride, wptr, wbytes)
+
+
+def _decode_batch_out(out, q):
+    B, R, H, D = q.shape
+    if out is None:
+        out = torch.empty((B * R, H * D), dtype=q.dtype, device=q.device)
+    assert out.dtype == q.dtype and out.shape == (B * R, H * D) and out.stride(1) == 1
+    return out, out.stride(0) if B * R > 1 else H * D
+
+
+@_on_device
+def attn_decode_fp8kv_batch(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.Tensor, n_keys: torch.Tensor = None,
+                            causal: bool = True, softmax_scale: float = None, out: torch.Tensor = None,
+                            workspace: torch.Tensor = None) -> torch.Tensor:
+    """``attn_decode_fp8kv`` for B sequences in one pair of launches (``mq_attn_decode_fp8kv_batch``): q [B, R, heads, 128] (a view of
+    the [B * R, ...] fused projection works), kv_cache [B, capacity, 2 * kv_heads, 128] float8_e4m3fn (a sequence's cache may be
+    padded: only stride(0) >= capacity * stride(1) is asked), kv_scale [2 * kv_heads] shared by the sequences, n_keys an int32 CUDA
+    tensor [B] read on the device (None: every sequence holds ``capacity`` keys) -> [B * R, heads * 128].  Sequence b's rows are
+    the bits ``attn_decode_fp8kv(q[b], kv_cache[b], ..., n_keys=n_keys[b])`` gives under the same plan."""
+    _need_cuda(q, kv_cache, kv_scale, out, workspace, n_keys)
+    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, torch.float8_e4m3fn)
+    out, ldo = _decode_batch_out(out, q)
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    call("mq_attn_decode_fp8kv_batch", q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq,
+         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, out.data_ptr(), ldo, wptr, wbytes, _stream())
+    return out
+
+
+@_on_device
+def attn_decode_batch(q: torch.Tensor, kv_cache: torch.Tensor, n_keys: torch.Tensor = None, causal: bool = True,
+                      softmax_scale: float = None, out: torch.Tensor = None, workspace: torch.Tensor = None) -> torch.Tensor:
+    """``attn_decode_fp8kv_batch`` over 16-bit caches (``mq_attn_decode_batch``): kv_cache [B, capacity, 2 * kv_heads, 128] in q's
+    dtype, no scales."""
+    _need_cuda(q, kv_cache, out, workspace, n_keys)
+    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, None, n_keys, workspace, q.dtype)
+    out, ldo = _decode_batch_out(out, q)
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    call("mq_attn_decode_batch", q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq,
+         float(softmax_scale), 1 if causal else 0, out.data_ptr(), ldo, wptr, wbytes, _stream())
+    return out
+
+
+@_on_device
+def attn_decode_quant_i8_batch(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.Tensor, scale0: float,
+                               scale1: Optional[float] = None, *, n_keys: torch.Tensor = None, causal: bool = True,
+                               softmax_scale: float = None, row_sel: Optional[torch.Tensor] = None, out=None, tiled: bool = False,
+                               workspace: torch.Tensor = None):
+    """``attn_decode_quant_i8`` for B sequences (``mq_attn_decode_fp8kv_quant_i8_batch``; kv_scale = None with caches of q's dtype:
+    ``mq_attn_decode_quant_i8_batch``): the int8 activations ``quantize_act_i8`` would produce from the [B * R, heads * 128] output of
+    the unfused batched call under the same plan, row-major or a ``TiledAct`` of B * R rows; row_sel: uint8 [B * R]."""
+    _need_cuda(q, kv_cache, kv_scale, row_sel, out, workspace, n_keys)
+    fp8 = kv_cache.dtype == torch.float8_e4m3fn and kv_scale is not None
+    assert fp8 or (kv_scale is None and kv_cache.dtype == q.dtype), \
+        f"kv_cache / kv_scale: float8_e4m3fn caches with their kv_scale, or caches of q's dtype ({q.dtype}) with kv_scale = None " \
+        f"(got {kv_cache.dtype}, kv_scale {'given' if kv_scale is not None else 'None'})"
+    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, kv_cache.dtype)
+    out, optr, K_pad, ldo = _out_act(out, tiled, B * R, H * D, q.device)
+    if softmax_scale is None:
+        softmax_scale = D ** -0.5
+    head = (q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq)
+    tail = (float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo, wptr, wbytes,
+            _stream())
+    if fp8:
+        call("mq_attn_decode_fp8kv_quant_i8_batch", *head, kv_scale.data_ptr(), *tail)
+    else:
+        call("mq_attn_decode_quant_i8_batch", *head, *tail)
+    return out
+
+
+@_on_device
+def kv_append_rope_fp8_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv_scale: torch.Tensor, cos: torch.Tensor = None,
+                             sin: torch.Tensor = None, n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
+    """``kv_append_rope_fp8`` for B sequences in one launch (``mq_kv_append_rope_fp8_batch``): qkv [B * R, (heads + 2 * kv_heads) * D],
+    rows [b R, (b + 1) R) the R <= 8 new rows of sequence b, kv_cache [B, capacity, 2 * kv_heads, D] float8_e4m3fn; n_keys (the key
+    counts AFTER the append) and rope_delta: int32 CUDA tensors [B] read on the device, None = the capacity / no offset.  Per
+    sequence the bits and bytes of the single-sequence call.  Returns qkv."""
+    assert kv_scale is not None
+    return _kv_append_batch(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, torch.float8_e4m3fn)
+
+
+@_on_device
+def kv_append_rope_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, cos: torch.Tensor = None, sin: torch.Tensor = None,
+                         n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
+    """``kv_append_rope_fp8_batch`` into 16-bit caches (``mq_kv_append_rope_batch``): kv_cache [B, capacity, 2 * kv_heads, D] in qkv's
+    dtype, no scales."""
+    return _kv_append_batch(qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta, qkv.dtype)
+
+
+def _kv_append_batch(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, storage):
+    _need_cuda(qkv, kv_cache, kv_scale, cos, sin, n_keys, rope_delta)
+    B, cap, H2, D, ldkv, seq = _batch_cache(kv_cache, storage)
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (heads + H2) * D and qkv.shape[0] % B == 0, \
+        f"qkv must be [B * R, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}] with B = {B} (got {tuple(qkv.shape)})"
+    R = qkv.shape[0] // B
+    if kv_scale is not None:
+        _check_kv_scale(kv_scale, H2 // 2)
+    n_dev, d_dev = _batch_counts(n_keys, B, "n_keys"), _batch_counts(rope_delta, B, "rope_delta")
+    assert (cos is None) == (sin is None), "cos and sin: both or neither"
+    rows = 0
+    if cos is not None:
+        assert cos.dtype == qkv.dtype == sin.dtype and cos.dim() == 2 and cos.shape[1] == D and cos.shape == sin.shape
+        assert cos.is_contiguous() and sin.is_contiguous()
+        rows = cos.shape[0]
+    else:
+        d_dev = None
+    args = (qkv.data_ptr(), dtype_code(qkv.dtype), B, R, cap, _ptr(n_dev), _ptr(d_dev), heads, H2 // 2, D,
+            qkv.stride(0) if B * R > 1 else qkv.shape[1], _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(), ldkv, seq)
+    if kv_scale is not None:
+        call("mq_kv_append_rope_fp8_batch", *args, kv_scale.data_ptr(), _stream())
+    else:
+        call("mq_kv_append_rope_batch", *args, _stream())
+    return qkv
+
+
+@_on_device
+def embed_gather_batch(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = None, id_log: torch.Tensor = None,
+                       n_keys: torch.Tensor = None) -> torch.Tensor:
+    """``embed_gather`` for B <= 8 sequences of one new row each (``mq_embed_gather_batch``): ids int32 [B] on the device -> [B, dim],
+    out[b] = table[clamp(ids[b])].  id_log: int32 [B, log_rows] (rows may be padded); the clamped id of sequence b goes to
+    id_log[b, n_b - 1], n_b = clamp(n_keys[b], 1, log_rows) for an int32 CUDA tensor [B], log_rows for None."""
+    _need_cuda(table, ids, out, id_log, n_keys)
+    vocab, dim = table.shape
+    assert table.stride(1) == 1 and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
+    B = ids.shape[0]
+    if out is None:
+        out = torch.empty((B, dim), dtype=table.dtype, device=table.device)
+    assert out.dtype == table.dtype and out.shape == (B, dim) and out.stride(1) == 1
+    ld_log = log_rows = 0
+    if id_log is not None:
+        assert id_log.dtype == torch.int32 and id_log.dim() == 2 and id_log.shape[0] == B and id_log.stride(1) == 1
+        log_rows = id_log.shape[1]
+        ld_log = id_log.stride(0) if B > 1 else log_rows
+    n_dev = _batch_counts(n_keys, B, "n_keys")
+    call("mq_embed_gather_batch", table.data_ptr(), dtype_code(table.dtype), vocab, dim, table.stride(0) if vocab > 1 else dim,
+         ids.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1 else dim, _ptr(id_log), ld_log, log_rows, _ptr(n_dev), _stream())
+    return out
+
+
 def _device_int(v, name: str, device) -> Optional[torch.Tensor]:
     """A device-side integer argument: an int32 CUDA tensor of one element as it is, a Python int as a fresh one (a fill on the current
     stream: keep a tensor of your own for a step that must not allocate), None as None."""

@@ -1,6 +1,6 @@
 """A greedy generation loop that never leaves the device: the step feeds itself.
 
-``Fp8KVCache`` and ``KVCache16`` made the middle of a generation step capturable (the length lives on the device); ``GreedyLoop`` closes both ends with
+The cache classes made the middle of a generation step capturable (the length lives on the device); the loop closes both ends with
 ONE int32 ``token`` on the device, as ``n_keys`` already is:
 
     cache.advance(1)                                             # n_keys += 1
@@ -11,7 +11,12 @@ ONE int32 ``token`` on the device, as ``n_keys`` already is:
 
 One linear chain of launches, captured once and replayed N times for N tokens; the host reads the ids afterwards from the log,
 which is indexed by cache position -- one copy, the single synchronisation.  Greedy selection only: no sampling, no EOS handling
-(inspect the ids between batches of replays)."""
+(inspect the ids between batches of replays).
+
+``_GreedyLoop`` holds the step, its capture and the replay loop once, over B sequences: ``GreedyLoopBatch`` is it for the batched
+caches, and ``GreedyLoop`` is it for one sequence, which the shared code sees as a batch of one through views (``ids[None]``,
+``cache[None]``) while ``token`` [1], ``ids`` [capacity], ``pos`` (an int) and the gather op (``ops.embed_gather``) stay the single
+sequence's own."""
 from __future__ import annotations
 
 from typing import Callable, Optional, Union
@@ -23,23 +28,86 @@ from . import ops
 from .kv_cache import Fp8KVCache, Fp8KVCacheBatch, KVCache16, KVCache16Batch
 
 
-class GreedyLoop:
-    def __init__(self, cache: Union[Fp8KVCache, KVCache16], embed_tokens: torch.Tensor, lm_head: torch.Tensor,
-                 body: Callable[[torch.Tensor], torch.Tensor], eps: float = 1e-6):
-        """cache: either cache class -- the loop touches ``dtype``, ``capacity``, ``n_keys``, ``caches``, ``advance`` and ``set_length``
-        only, and the body calls the cache's own ``step``.  embed_tokens [vocab, dim] and lm_head [vocab_out, dim]: fp16 / bf16 CUDA tensors of the cache's dtype.  body: hidden
-        [1, dim] -> [1, dim], the decoder layers of ONE new position; for a step that is to be captured it must neither synchronise
-        nor depend on host state that changes between steps."""
+class _GreedyLoop:
+    def __init__(self, cache, embed_tokens: torch.Tensor, lm_head: torch.Tensor, body: Callable[[torch.Tensor], torch.Tensor], eps: float,
+                 batch: Optional[int]):
+        """batch: None = one sequence (``token`` [1], ``ids`` [capacity], ``pos`` an int), B = a batched cache's B sequences
+        (``token`` [B], ``ids`` [B, capacity], ``pos`` a list)."""
         assert embed_tokens.dim() == 2 and lm_head.dim() == 2 and embed_tokens.shape[1] == lm_head.shape[1]
         assert embed_tokens.dtype == lm_head.dtype == cache.dtype and embed_tokens.device == lm_head.device == cache.n_keys.device
         self.cache, self.embed_tokens, self.lm_head, self.body, self.eps = cache, embed_tokens, lm_head, body, eps
         self.dim = embed_tokens.shape[1]
-        dev = embed_tokens.device
-        self.token = torch.zeros((1,), dtype=torch.int32, device=dev)              # the id the next step embeds
-        self.ids = torch.zeros((cache.capacity,), dtype=torch.int32, device=dev)   # ids[t] = the id embedded at cache position t
-        self.hidden = torch.empty((1, self.dim), dtype=embed_tokens.dtype, device=dev)
+        dev, lead = embed_tokens.device, () if batch is None else (batch,)
+        self.token = torch.zeros(lead or (1,), dtype=torch.int32, device=dev)             # the id(s) the next step embeds
+        self.ids = torch.zeros(lead + (cache.capacity,), dtype=torch.int32, device=dev)   # ids[(b,) t] = the id embedded at cache position t
+        self.hidden = torch.empty((batch or 1, self.dim), dtype=embed_tokens.dtype, device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.pos = 0                 # host side: the cache position of the next step (the host issues the steps, so it knows)
+        self.pos = 0 if batch is None else [0] * batch   # host side: the cache position of the next step (the host issues the steps, so it knows)
+        self._batched, self._gather = batch is not None, ops.embed_gather if batch is None else ops.embed_gather_batch
+
+    def _by_sequence(self, t: torch.Tensor) -> torch.Tensor:
+        """The log or a cache as [sequence, position, ...]: one sequence is a batch of one."""
+        return t if self._batched else t[None]
+
+    def step(self) -> None:
+        """One position (of every sequence), on the current stream: capturable (after one warm-up step it neither allocates outside
+        torch's own ops nor synchronises).  Does not move ``pos``: ``generate`` counts the steps."""
+        self.cache.advance(1)
+        self._gather(self.embed_tokens, self.token, out=self.hidden, id_log=self.ids, n_keys=self.cache.n_keys)
+        h = self.body(self.hidden)
+        h = F.rms_norm(h, (self.dim,), eps=self.eps)
+        ops.gemv_f16_argmax(h, self.lm_head, token_out=self.token)
+
+    def capture(self) -> None:
+        """Warm up (workspaces, one-time checks) and capture ``step`` once, on a side stream.  Everything the warm-up step wrote is
+        restored afterwards -- ``n_keys``, ``token`` and, for every sequence, the cache row and the log entry of its own position --
+        so this may come before or after ``start`` and before or after the prefill.  Set-up, not the loop: it reads ``n_keys`` back
+        once."""
+        n_keys, token = self.cache.n_keys.clone(), self.token.clone()
+        at = [min(max(n + 1, 1), self.cache.capacity) - 1 for n in n_keys.cpu().tolist()]     # the positions the kernels' clamps give the warm-up
+        seqs = list(range(len(at)))
+        caches, ids = [self._by_sequence(c).view(torch.uint8) for c in self.cache.caches], self._by_sequence(self.ids)
+        rows, logged = [c[seqs, at] for c in caches], ids[seqs, at]                           # copies (indexed by lists)
+        side = torch.cuda.Stream(device=self.token.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self.step()
+        torch.cuda.current_stream().wait_stream(side)
+        self.cache.n_keys.copy_(n_keys)
+        self.token.copy_(token)
+        ids[seqs, at] = logged
+        for c, row in zip(caches, rows):
+            c[seqs, at] = row
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            self.step()
+        self.graph = graph
+
+    def generate(self, n: int) -> torch.Tensor:
+        """n more positions (graph replays once captured, eager steps before) -> the ids embedded at them, an int32 CPU tensor [n]
+        (B sequences: [B, n], row b from sequence b's own position on): after ``start`` entry 0 is the first token, and the n-th
+        generated id is left in ``token``.  The copy is the only synchronisation."""
+        first = self.pos if self._batched else [self.pos]
+        assert n >= 0 and max(first) + n <= self.cache.capacity, f"{n} steps from position {self.pos} exceed the cache's {self.cache.capacity} rows"
+        run = self.graph.replay if self.graph is not None else self.step
+        for _ in range(n):
+            run()
+        if not self._batched:
+            self.pos += n
+            return self.ids[first[0]:first[0] + n].cpu()
+        self.pos = [p + n for p in first]
+        ids = self.ids.cpu()
+        return torch.stack([ids[b, p:p + n] for b, p in enumerate(first)])
+
+
+class GreedyLoop(_GreedyLoop):
+    def __init__(self, cache: Union[Fp8KVCache, KVCache16], embed_tokens: torch.Tensor, lm_head: torch.Tensor,
+                 body: Callable[[torch.Tensor], torch.Tensor], eps: float = 1e-6):
+        """cache: either single-sequence cache class -- the loop touches ``dtype``, ``capacity``, ``n_keys``, ``caches``, ``advance`` and
+        ``set_length`` only, and the body calls the cache's own ``step``.  embed_tokens [vocab, dim] and lm_head [vocab_out, dim]:
+        fp16 / bf16 CUDA tensors of the cache's dtype.  body: hidden [1, dim] -> [1, dim], the decoder layers of ONE new position; for
+        a step that is to be captured it must neither synchronise nor depend on host state that changes between steps."""
+        super().__init__(cache, embed_tokens, lm_head, body, eps, None)
 
     def start(self, prompt_len: int, first_token: int) -> None:
         """The prefill wrote cache rows [0, prompt_len) and picked first_token: the next step embeds it at position prompt_len."""
@@ -48,73 +116,17 @@ class GreedyLoop:
         self.token.fill_(int(first_token))
         self.pos = prompt_len
 
-    def step(self) -> None:
-        """One position, on the current stream: capturable (after one warm-up step it neither allocates outside torch's own ops nor
-        synchronises).  Does not move ``pos``: ``generate`` counts the steps."""
-        self.cache.advance(1)
-        ops.embed_gather(self.embed_tokens, self.token, out=self.hidden, id_log=self.ids, n_keys=self.cache.n_keys)
-        h = self.body(self.hidden)
-        h = F.rms_norm(h, (self.dim,), eps=self.eps)
-        ops.gemv_f16_argmax(h, self.lm_head, token_out=self.token)
 
-    def capture(self) -> None:
-        """Warm up (workspaces, one-time checks) and capture ``step`` once, on a side stream.  Everything the warm-up step wrote is
-        restored afterwards -- ``n_keys``, ``token``, the cache row and the log entry of its position -- so this may come before
-        or after ``start`` and before or after the prefill.  Set-up, not the loop: it reads ``n_keys`` back once."""
-        n_keys, token = self.cache.n_keys.clone(), self.token.clone()
-        at = min(max(int(n_keys.item()) + 1, 1), self.cache.capacity) - 1          # the position the kernels' clamp gives the warm-up
-        rows, logged = [c[at].clone() for c in self.cache.caches], self.ids[at].clone()
-        side = torch.cuda.Stream(device=self.token.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.step()
-        torch.cuda.current_stream().wait_stream(side)
-        self.cache.n_keys.copy_(n_keys)
-        self.token.copy_(token)
-        self.ids[at].copy_(logged)
-        for c, row in zip(self.cache.caches, rows):
-            c[at].copy_(row)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            self.step()
-        self.graph = graph
-
-    def generate(self, n: int) -> torch.Tensor:
-        """n more positions (graph replays once captured, eager steps before) -> the ids embedded at them, an int32 CPU tensor [n]:
-        after ``start`` entry 0 is first_token, and the n-th generated id is left in ``token``.  The copy is the only synchronisation."""
-        assert n >= 0 and self.pos + n <= self.cache.capacity, f"{n} steps from position {self.pos} exceed the cache's {self.cache.capacity} rows"
-        run = self.graph.replay if self.graph is not None else self.step
-        for _ in range(n):
-            run()
-        first, self.pos = self.pos, self.pos + n
-        return self.ids[first:first + n].cpu()
-
-
-class GreedyLoopBatch:
-    """``GreedyLoop`` for B <= 8 sequences that step together over a batched cache: one weight pass of the body and of lm_head
-    serves B tokens.  ``token`` [B], ``ids`` [B, capacity] (ids[b, t] = the id sequence b embedded at its cache position t) and
-    ``hidden`` [B, dim] live on the device; the step is
-
-        cache.advance(1)                                          # every n_keys[b] += 1
-        hidden[b] = embed_tokens[token[b]]; ids[b, n_keys[b] - 1] = token[b]      # ops.embed_gather_batch
-        h = rms_norm(body(hidden))                                # body: [B, dim] -> [B, dim]; it calls the batched cache's step
-        token = argmax(h @ lm_head.t())                           # ops.gemv_f16_argmax at M = B
-
-    All sequences step together: no stop ids, no per-sequence masks, no sampling."""
+class GreedyLoopBatch(_GreedyLoop):
+    """``GreedyLoop`` for B <= 8 sequences that step together over a batched cache: one weight pass of the body (hidden [B, dim] ->
+    [B, dim]; it calls the batched cache's step) and of lm_head (``ops.gemv_f16_argmax`` at M = B) serves B tokens; the gather is
+    ``ops.embed_gather_batch``.  All sequences step together: no stop ids, no per-sequence masks, no sampling."""
 
     def __init__(self, cache: Union[Fp8KVCacheBatch, KVCache16Batch], embed_tokens: torch.Tensor, lm_head: torch.Tensor,
                  body: Callable[[torch.Tensor], torch.Tensor], eps: float = 1e-6):
-        assert embed_tokens.dim() == 2 and lm_head.dim() == 2 and embed_tokens.shape[1] == lm_head.shape[1]
-        assert embed_tokens.dtype == lm_head.dtype == cache.dtype and embed_tokens.device == lm_head.device == cache.n_keys.device
         assert 1 <= cache.batch <= 8, f"a batch of {cache.batch} sequences (1 .. 8: the rows of ops.embed_gather_batch and ops.gemv_f16_argmax)"
-        self.cache, self.embed_tokens, self.lm_head, self.body, self.eps = cache, embed_tokens, lm_head, body, eps
-        self.batch, self.dim = cache.batch, embed_tokens.shape[1]
-        dev = embed_tokens.device
-        self.token = torch.zeros((self.batch,), dtype=torch.int32, device=dev)                    # the ids the next step embeds
-        self.ids = torch.zeros((self.batch, cache.capacity), dtype=torch.int32, device=dev)
-        self.hidden = torch.empty((self.batch, self.dim), dtype=embed_tokens.dtype, device=dev)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.pos = [0] * self.batch  # host side: every sequence's cache position of the next step
+        super().__init__(cache, embed_tokens, lm_head, body, eps, cache.batch)
+        self.batch = cache.batch
 
     def start(self, prompt_lens, first_tokens) -> None:
         """The prefill wrote rows [0, prompt_lens[b]) of sequence b's caches and picked first_tokens[b]."""
@@ -125,45 +137,3 @@ class GreedyLoopBatch:
         self.cache.set_length(prompt_lens)
         self.token.copy_(torch.tensor(first_tokens, dtype=torch.int32))
         self.pos = prompt_lens
-
-    def step(self) -> None:
-        """One position of every sequence, on the current stream: capturable.  Does not move ``pos``."""
-        self.cache.advance(1)
-        ops.embed_gather_batch(self.embed_tokens, self.token, out=self.hidden, id_log=self.ids, n_keys=self.cache.n_keys)
-        h = self.body(self.hidden)
-        h = F.rms_norm(h, (self.dim,), eps=self.eps)
-        ops.gemv_f16_argmax(h, self.lm_head, token_out=self.token)
-
-    def capture(self) -> None:
-        """``GreedyLoop.capture`` per sequence: warm up, restore everything the warm-up step wrote -- ``n_keys``, ``token`` and, for
-        every sequence, the cache row and the log entry of its own position -- then capture ``step`` once."""
-        n_keys, token = self.cache.n_keys.clone(), self.token.clone()
-        at = [min(max(n + 1, 1), self.cache.capacity) - 1 for n in n_keys.cpu().tolist()]     # the positions the kernels' clamps give
-        seqs = list(range(self.batch))
-        rows, logged = [c.view(torch.uint8)[seqs, at] for c in self.cache.caches], self.ids[seqs, at]     # copies (indexed by lists)
-        side = torch.cuda.Stream(device=self.token.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.step()
-        torch.cuda.current_stream().wait_stream(side)
-        self.cache.n_keys.copy_(n_keys)
-        self.token.copy_(token)
-        self.ids[seqs, at] = logged
-        for c, row in zip(self.cache.caches, rows):
-            c.view(torch.uint8)[seqs, at] = row
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            self.step()
-        self.graph = graph
-
-    def generate(self, n: int) -> torch.Tensor:
-        """n more positions of every sequence -> int32 CPU [B, n]: row b holds the ids embedded at positions pos_b .. pos_b + n - 1
-        (after ``start`` column 0 is first_tokens); the n-th generated ids are left in ``token``.  The copy is the only synchronisation."""
-        assert n >= 0 and max(self.pos) + n <= self.cache.capacity, \
-            f"{n} steps from positions {self.pos} exceed the cache's {self.cache.capacity} rows"
-        run = self.graph.replay if self.graph is not None else self.step
-        for _ in range(n):
-            run()
-        first, self.pos = self.pos, [p + n for p in self.pos]
-        ids = self.ids.cpu()
-        return torch.stack([ids[b, first[b]:first[b] + n] for b in range(self.batch)])

@@ -1,6 +1,10 @@
 """Torch-tensor front-end of the C ABI.  PyTorch is plumbing here (device memory and
 streams); every function below launches hand-written gfx950 kernels through
 ``include/mquant_hip.h`` and has no eager/CPU fallback.
+
+The twelve ops of a generation step (``attn_decode*``, ``kv_append_rope*``, ``embed_gather*``: one sequence or a batch, an e4m3 or a
+16-bit cache, a 16-bit or a fused int8 destination) are a docstring and one call each: ``_attn_decode``, ``_kv_append`` and
+``_embed_gather`` hold the checks and build the C argument list once per operation, seeing one sequence as a batch of one.
 """
 from __future__ import annotations
 
@@ -583,6 +587,21 @@ def embed_gather(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = 
     rows clamp(id, 0, vocab - 1).  id_log: an int32 [log_rows] CUDA tensor that also receives the clamped id of row r at
     [n - R + r], n = clamp(n_keys, R, log_rows) for an int32 CUDA tensor of one element (``Fp8KVCache.n_keys`` AFTER ``advance``: the
     log is indexed by cache position), n = log_rows for None."""
+    return _embed_gather(False, table, ids, out, id_log, n_keys)
+
+
+@_on_device
+def embed_gather_batch(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = None, id_log: torch.Tensor = None,
+                       n_keys: torch.Tensor = None) -> torch.Tensor:
+    """``embed_gather`` for B <= 8 sequences of one new row each (``mq_embed_gather_batch``): ids int32 [B] on the device -> [B, dim],
+    out[b] = table[clamp(ids[b])].  id_log: int32 [B, log_rows] (rows may be padded); the clamped id of sequence b goes to
+    id_log[b, n_b - 1], n_b = clamp(n_keys[b], 1, log_rows) for an int32 CUDA tensor [B], log_rows for None."""
+    return _embed_gather(True, table, ids, out, id_log, n_keys)
+
+
+def _embed_gather(batched: bool, table, ids, out, id_log, n_keys):
+    """The two gathers: the checks and the call.  The rows are the R rows of one sequence or one row of each of B sequences; the
+    1-D log of one sequence is a 2-D log of one row whose row stride (the C argument ``ld_log``) is absent."""
     _need_cuda(table, ids, out, id_log, n_keys)
     vocab, dim = table.shape
     assert table.stride(1) == 1 and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
@@ -590,14 +609,16 @@ def embed_gather(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = 
     if out is None:
         out = torch.empty((R, dim), dtype=table.dtype, device=table.device)
     assert out.dtype == table.dtype and out.shape == (R, dim) and out.stride(1) == 1
-    log_rows = 0
+    ld_log = log_rows = 0
     if id_log is not None:
-        assert id_log.dtype == torch.int32 and id_log.dim() == 1 and id_log.is_contiguous()
-        log_rows = id_log.shape[0]
-    assert n_keys is None or (isinstance(n_keys, torch.Tensor) and n_keys.dtype == torch.int32 and n_keys.numel() == 1), \
-        "n_keys: an int32 CUDA tensor of one element or None"
-    call("mq_embed_gather", table.data_ptr(), dtype_code(table.dtype), vocab, dim, table.stride(0) if vocab > 1 else dim,
-         ids.data_ptr(), R, out.data_ptr(), out.stride(0) if R > 1 else dim, _ptr(id_log), log_rows, _ptr(n_keys), _stream())
+        assert id_log.dtype == torch.int32 and ((id_log.dim() == 2 and id_log.shape[0] == R and id_log.stride(1) == 1) if batched
+                                                else (id_log.dim() == 1 and id_log.is_contiguous()))
+        log_rows = id_log.shape[-1]
+        ld_log = id_log.stride(0) if batched and R > 1 else log_rows
+    _device_counts(n_keys, R if batched else 1, "n_keys", None if batched else "an int32 CUDA tensor of one element or None")
+    call("mq_embed_gather_batch" if batched else "mq_embed_gather", table.data_ptr(), dtype_code(table.dtype), vocab, dim,
+         table.stride(0) if vocab > 1 else dim, ids.data_ptr(), R, out.data_ptr(), out.stride(0) if R > 1 else dim, _ptr(id_log),
+         *((ld_log,) if batched else ()), log_rows, _ptr(n_keys), _stream())
     return out
 
 
@@ -635,8 +656,57 @@ def attn_prefill_quant_i8(q: torch.Tensor, scale0: float, scale1: Optional[float
     return out
 
 
+# --------------------------------------------------------------------------- the generation step
+# Twelve public ops over one sequence or a batch of B, an e4m3 or a 16-bit cache, a 16-bit or a fused int8 destination: each is a
+# docstring and one call of _attn_decode, _kv_append or _embed_gather, which hold the checks and build the C arguments once.  The
+# flags choose the pieces of the argument list and the entry point's name; no op borrows another's entry point.
 _DECODE_WS = {}
 _DECODE_PINNED = []      # outgrown decode workspaces that a captured hipGraph may still replay into (as _SPLITK_PINNED)
+_E4M3 = torch.float8_e4m3fn
+
+
+# The packed-stride rule, written ``stride if size > 1 else packed`` wherever a stride is passed: torch reports arbitrary strides for
+# dimensions of size 1 (a one-row slice keeps its buffer's row stride, a fresh [1, n] tensor may report n or 1) while the entry points
+# check every stride they are given, so for such a dimension the wrappers pass the packed stride instead.  (Spelled out at each place,
+# like the view of one sequence as a batch of one, because a helper per stride was measurable in a step's host time.)
+
+
+_ONE_INT = "an int or an int32 CUDA tensor of one element"       # what a single-sequence op takes for a device-side integer
+
+
+def _device_counts(v, n: int, name: str, one: Optional[str] = None) -> Optional[torch.Tensor]:
+    """An integer per sequence that a kernel reads on the device: None, or an int32 CUDA tensor of n elements (contiguous).  one: the
+    refusal's wording for a single-sequence op (n = 1), which may take an int as well; None = a batch of B = n."""
+    assert v is None or (isinstance(v, torch.Tensor) and v.dtype == torch.int32 and v.is_cuda and v.numel() == n and v.is_contiguous()), \
+        f"{name}: " + (one or f"None or a contiguous int32 CUDA tensor of B = {n} elements")
+    return v
+
+
+def _device_int(v, name: str, device) -> Optional[torch.Tensor]:
+    """A device-side integer argument of a single-sequence op: an int32 CUDA tensor of one element as it is, a Python int as a fresh
+    one (a fill on the current stream: keep a tensor of your own for a step that must not allocate), None as None."""
+    if v is None or isinstance(v, torch.Tensor):
+        return _device_counts(v, 1, name, _ONE_INT)
+    return torch.full((1,), int(v), dtype=torch.int32, device=device)
+
+
+def _cache_and_count(kv_cache, n_keys, batched: bool, storage):
+    """What the attention and the append share: (B, capacity, 2 kv_heads, D, ldkv, seq_stride, T, n_keys on the device or None) of a
+    cache [B, capacity, 2 * kv_heads, D] -- one sequence's [capacity, ...] is a batch of one -- and its key count.  Strides in
+    elements.  n_keys of one sequence: an int (T), a tensor of one element, or None; of a batch: a tensor of B elements or None.  T
+    is the capacity whenever the count lives on the device, and for None."""
+    if batched:
+        (B, cap, H2, D), (seq, ldkv, sh, sd) = kv_cache.shape, kv_cache.stride()
+    else:
+        (cap, H2, D), (ldkv, sh, sd), B, seq = kv_cache.shape, kv_cache.stride(), 1, 0
+    assert H2 % 2 == 0 and kv_cache.dtype == storage and sd == 1 and sh == D
+    ldkv = ldkv if cap > 1 else H2 * D
+    seq = seq if B > 1 else cap * ldkv
+    if batched or n_keys is None or isinstance(n_keys, torch.Tensor):
+        return B, cap, H2, D, ldkv, seq, cap, _device_counts(n_keys, B, "n_keys", None if batched else _ONE_INT)
+    T = int(n_keys)
+    assert T <= cap, f"n_keys = {T} exceeds the cache's capacity {cap}"
+    return B, cap, H2, D, ldkv, seq, T, None
 
 
 def attn_decode_workspace_bytes(R: int, T: int, heads: int, kv_heads: int) -> int:
@@ -645,17 +715,32 @@ def attn_decode_workspace_bytes(R: int, T: int, heads: int, kv_heads: int) -> in
     return int(_lib.load().mq_attn_decode_workspace_bytes(R, T, heads, kv_heads))
 
 
+def attn_decode_batch_workspace_bytes(B: int, R: int, T: int, heads: int, kv_heads: int) -> int:
+    """Bytes of workspace a batched decode attention call needs (``mq_attn_decode_batch_workspace_bytes``).  Host arithmetic only."""
+    return int(_lib.load().mq_attn_decode_batch_workspace_bytes(B, R, T, heads, kv_heads))
+
+
 def attn_decode_debug_force(splits: int = 0, keys_per_split: int = 0) -> None:
     """Test hook: force the key ranges / keys per range of the decode attention (0 = the heuristic)."""
     call("mq_attn_decode_debug_force", splits, keys_per_split)
 
 
-def attn_decode_plan(R: int, T: int, heads: int, kv_heads: int) -> dict:
-    """What the host decides for a decode attention call (``mq_attn_decode_debug_plan``); raises for arguments the call refuses."""
+def _decode_plan(entry: str, *dims) -> dict:
     import ctypes
     plan = (ctypes.c_int * 5)()
-    call("mq_attn_decode_debug_plan", R, T, heads, kv_heads, ctypes.cast(plan, ctypes.c_void_p))
+    call(entry, *dims, ctypes.cast(plan, ctypes.c_void_p))
     return dict(zip(("splits", "keys_per_split", "grid", "passes", "workspace_bytes"), plan))
+
+
+def attn_decode_plan(R: int, T: int, heads: int, kv_heads: int) -> dict:
+    """What the host decides for a decode attention call (``mq_attn_decode_debug_plan``); raises for arguments the call refuses."""
+    return _decode_plan("mq_attn_decode_debug_plan", R, T, heads, kv_heads)
+
+
+def attn_decode_batch_plan(B: int, R: int, T: int, heads: int, kv_heads: int) -> dict:
+    """``attn_decode_plan`` of a batched call (``mq_attn_decode_batch_debug_plan``): splits, keys_per_split and passes per sequence,
+    grid and workspace_bytes for the whole batch."""
+    return _decode_plan("mq_attn_decode_batch_debug_plan", B, R, T, heads, kv_heads)
 
 
 def _decode_workspace(device, nbytes: int) -> torch.Tensor:
@@ -674,29 +759,49 @@ def _decode_workspace(device, nbytes: int) -> torch.Tensor:
     return ent[0]
 
 
-def _decode_args(q, kv_cache, kv_scale, n_keys, workspace, storage=torch.float8_e4m3fn):
-    """The arguments the decode entry points share: (R, T, n_keys_dev, heads, kv_heads, ldq, ldkv, workspace ptr, bytes).  storage:
-    the cache's dtype -- float8_e4m3fn with kv_scale, or q's dtype without (ldkv is in elements either way)."""
-    R, H, D = q.shape
-    cap, H2, D2 = kv_cache.shape
-    assert D2 == D and H2 % 2 == 0 and kv_cache.dtype == storage
-    assert q.stride(2) == 1 and q.stride(1) == D and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
+def _attn_decode(batched: bool, fp8: Optional[bool], q, kv_cache, kv_scale, n_keys, causal, softmax_scale, out, workspace, quant=None):
+    """The six decode attention ops: the checks, the key count, the workspace, the destination and the call.  batched: q
+    [B, R, heads, D] over caches [B, capacity, ...] with B counts, else q [R, heads, D] over one cache, seen as a batch of one.  fp8:
+    an e4m3 cache with kv_scale, or one of q's dtype without; None = whichever the arguments are (the fused ops take both).  quant:
+    None for a 16-bit ``out``, or (scale0, scale1, row_sel, tiled) of the fused int8 quantizer."""
+    _need_cuda(q, kv_cache, kv_scale, quant and quant[2], out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
+    if fp8 is None:
+        fp8 = kv_cache.dtype == _E4M3 and kv_scale is not None
+        assert fp8 or (kv_scale is None and kv_cache.dtype == q.dtype), \
+            f"kv_cache / kv_scale: a float8_e4m3fn cache with its kv_scale, or a cache of q's dtype ({q.dtype}) with kv_scale = None " \
+            f"(got {kv_cache.dtype}, kv_scale {'given' if kv_scale is not None else 'None'})"
+    if batched:
+        (B, R, H, D), (sb, ldq, sh, sd) = q.shape, q.stride()
+    else:                                                              # one sequence: a batch of one
+        (R, H, D), (ldq, sh, sd), B, sb = q.shape, q.stride(), 1, 0
+    B2, cap, H2, D2, ldkv, seq, T, n_dev = _cache_and_count(kv_cache, n_keys, batched, _E4M3 if fp8 else q.dtype)
+    assert B2 == B and D2 == D and sd == 1 and sh == D
+    ldq = ldq if R > 1 else (sb if B > 1 else H * D)   # the rows of a sequence ldq apart, the sequences R * ldq apart: a view of [B * R, ...]
+    assert B == 1 or sb == R * ldq, "q: the B * R rows must be one row stride apart (a view of a [B * R, ...] tensor)"
     hkv = H2 // 2
-    if storage == torch.float8_e4m3fn:
+    if fp8:
         _check_kv_scale(kv_scale, hkv)
     else:
-        assert kv_scale is None and storage == q.dtype
-    if isinstance(n_keys, torch.Tensor):
-        assert n_keys.dtype == torch.int32 and n_keys.numel() == 1 and n_keys.is_cuda, "n_keys: an int or an int32 CUDA tensor of one element"
-        T, n_dev = cap, n_keys.data_ptr()
-    else:
-        T, n_dev = (cap if n_keys is None else int(n_keys)), None
-        assert T <= cap, f"n_keys = {T} exceeds the cache's capacity {cap}"
-    need = attn_decode_workspace_bytes(R, T, H, hkv)
-    if workspace is None and need:
-        workspace = _decode_workspace(q.device, need)
+        assert kv_scale is None
+    if workspace is None:
+        need = attn_decode_batch_workspace_bytes(B, R, T, H, hkv) if batched else attn_decode_workspace_bytes(R, T, H, hkv)
+        if need:
+            workspace = _decode_workspace(q.device, need)
     wptr, wbytes = (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
-    return (R, T, n_dev, H, hkv, D, q.stride(0) if R > 1 else H * D, kv_cache.stride(0) if cap > 1 else H2 * D, wptr, wbytes)
+    if quant is None:
+        if out is None:
+            out = torch.empty((B * R, H * D), dtype=q.dtype, device=q.device)
+        assert out.dtype == q.dtype and out.shape == (B * R, H * D) and out.stride(1) == 1
+        dest = (out.data_ptr(), out.stride(0) if B * R > 1 else H * D)
+    else:
+        scale0, scale1, row_sel, tiled = quant
+        out, optr, K_pad, ldo = _out_act(out, tiled, B * R, H * D, q.device)
+        dest = (float(scale0), _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo)
+    call("mq_attn_decode" + ("_fp8kv" if fp8 else "") + ("_quant_i8" if quant else "") + ("_batch" if batched else ""),
+         q.data_ptr(), dtype_code(q.dtype), *((B,) if batched else ()), R, T, _ptr(n_dev), H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
+         *((seq,) if batched else ()), *((kv_scale.data_ptr(),) if fp8 else ()),
+         float(D ** -0.5 if softmax_scale is None else softmax_scale), 1 if causal else 0, *dest, wptr, wbytes, _stream())
+    return out
 
 
 @_on_device
@@ -708,17 +813,7 @@ def attn_decode_fp8kv(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torch.T
     -> [R, heads * 128].  n_keys: how many cache rows hold keys -- an int (default: the capacity) or an int32 CUDA tensor of one
     element, read on the device by the kernel (a captured generation step then replays while the cache grows).  causal: row r
     attends keys 0 .. n - R + r.  workspace: a buffer of at least ``attn_decode_workspace_bytes`` bytes instead of the wrapper's."""
-    _need_cuda(q, kv_cache, kv_scale, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
-    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace)
-    if out is None:
-        out = torch.empty((R, H * D), dtype=q.dtype, device=q.device)
-    assert out.dtype == q.dtype and out.shape == (R, H * D) and out.stride(1) == 1
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    call("mq_attn_decode_fp8kv", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
-         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, out.data_ptr(), out.stride(0) if R > 1 else H * D,
-         wptr, wbytes, _stream())
-    return out
+    return _attn_decode(False, True, q, kv_cache, kv_scale, n_keys, causal, softmax_scale, out, workspace)
 
 
 @_on_device
@@ -728,16 +823,7 @@ def attn_decode(q: torch.Tensor, kv_cache: torch.Tensor, n_keys=None, causal: bo
     then V heads, what ``kv_append_rope`` writes; the K|V columns of the fused q|k|v output work in place), no scales.  The kernel
     and its arithmetic are the e4m3 one's with both scales 1: equal cache values give equal bits.  n_keys, causal, workspace: as
     there."""
-    _need_cuda(q, kv_cache, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
-    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, None, n_keys, workspace, storage=q.dtype)
-    if out is None:
-        out = torch.empty((R, H * D), dtype=q.dtype, device=q.device)
-    assert out.dtype == q.dtype and out.shape == (R, H * D) and out.stride(1) == 1
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    call("mq_attn_decode", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
-         float(softmax_scale), 1 if causal else 0, out.data_ptr(), out.stride(0) if R > 1 else H * D, wptr, wbytes, _stream())
-    return out
+    return _attn_decode(False, False, q, kv_cache, None, n_keys, causal, softmax_scale, out, workspace)
 
 
 @_on_device
@@ -748,82 +834,7 @@ def attn_decode_quant_i8(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: torc
     (``mq_attn_decode_fp8kv_quant_i8``): returns the int8 activations ``quantize_act_i8`` would produce from the 16-bit decode
     output of the same plan ([R, heads * 128] row-major, or a ``TiledAct``).  kv_scale = None with a cache of q's dtype: the same
     over a 16-bit cache, ``attn_decode`` with the quantizer fused (``mq_attn_decode_quant_i8``)."""
-    _need_cuda(q, kv_cache, kv_scale, row_sel, out, workspace, n_keys if isinstance(n_keys, torch.Tensor) else None)
-    fp8 = kv_cache.dtype == torch.float8_e4m3fn and kv_scale is not None
-    assert fp8 or (kv_scale is None and kv_cache.dtype == q.dtype), \
-        f"kv_cache / kv_scale: a float8_e4m3fn cache with its kv_scale, or a cache of q's dtype ({q.dtype}) with kv_scale = None " \
-        f"(got {kv_cache.dtype}, kv_scale {'given' if kv_scale is not None else 'None'})"
-    R, T, n_dev, H, hkv, D, ldq, ldkv, wptr, wbytes = _decode_args(q, kv_cache, kv_scale, n_keys, workspace, storage=kv_cache.dtype)
-    out, optr, K_pad, ldo = _out_act(out, tiled, R, H * D, q.device)
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    if not fp8:
-        call("mq_attn_decode_quant_i8", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
-             float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo, wptr,
-             wbytes, _stream())
-        return out
-    call("mq_attn_decode_fp8kv_quant_i8", q.data_ptr(), dtype_code(q.dtype), R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv,
-         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel),
-         optr, K_pad, ldo, wptr, wbytes, _stream())
-    return out
-
-
-def attn_decode_batch_workspace_bytes(B: int, R: int, T: int, heads: int, kv_heads: int) -> int:
-    """Bytes of workspace a batched decode attention call needs (``mq_attn_decode_batch_workspace_bytes``).  Host arithmetic only."""
-    return int(_lib.load().mq_attn_decode_batch_workspace_bytes(B, R, T, heads, kv_heads))
-
-
-def attn_decode_batch_plan(B: int, R: int, T: int, heads: int, kv_heads: int) -> dict:
-    """``attn_decode_plan`` of a batched call (``mq_attn_decode_batch_debug_plan``): splits, keys_per_split and passes per sequence,
-    grid and workspace_bytes for the whole batch."""
-    import ctypes
-    plan = (ctypes.c_int * 5)()
-    call("mq_attn_decode_batch_debug_plan", B, R, T, heads, kv_heads, ctypes.cast(plan, ctypes.c_void_p))
-    return dict(zip(("splits", "keys_per_split", "grid", "passes", "workspace_bytes"), plan))
-
-
-def _batch_counts(v, B: int, name: str) -> Optional[torch.Tensor]:
-    """A per-sequence device integer of a batched call: None, or an int32 CUDA tensor of B elements (contiguous)."""
-    assert v is None or (isinstance(v, torch.Tensor) and v.dtype == torch.int32 and v.is_cuda and v.numel() == B and v.is_contiguous()), \
-        f"{name}: None or a contiguous int32 CUDA tensor of B = {B} elements"
-    return v
-
-
-def _batch_cache(kv_cache, storage):
-    """(B, capacity, 2 kv_heads, D, ldkv, seq_stride) of a batched cache [B, capacity, 2 * kv_heads, D]; strides in elements"""
-    B, cap, H2, D = kv_cache.shape
-    assert H2 % 2 == 0 and kv_cache.dtype == storage and kv_cache.stride(3) == 1 and kv_cache.stride(2) == D
-    ldkv = kv_cache.stride(1) if cap > 1 else H2 * D
-    return B, cap, H2, D, ldkv, kv_cache.stride(0) if B > 1 else cap * ldkv
-
-
-def _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, storage):
-    """``_decode_args`` of the batched entry points: (B, R, T, n_keys_dev, heads, kv_heads, D, ldq, ldkv, seq_stride, workspace ptr,
-    bytes).  q [B, R, heads, D]: the rows of a sequence ldq apart, the sequences R * ldq apart (a view of [B * R, ...])."""
-    B, R, H, D = q.shape
-    B2, cap, H2, D2, ldkv, seq_stride = _batch_cache(kv_cache, storage)
-    assert B2 == B and D2 == D and q.stride(3) == 1 and q.stride(2) == D
-    ldq = q.stride(1) if R > 1 else (q.stride(0) if B > 1 else H * D)
-    assert B == 1 or q.stride(0) == R * ldq, "q: the B * R rows must be one row stride apart (a view of a [B * R, ...] tensor)"
-    hkv = H2 // 2
-    if storage == torch.float8_e4m3fn:
-        _check_kv_scale(kv_scale, hkv)
-    else:
-        assert kv_scale is None and storage == q.dtype
-    n_dev = _batch_counts(n_keys, B, "n_keys")
-    need = attn_decode_batch_workspace_bytes(B, R, cap, H, hkv)
-    if workspace is None and need:
-        workspace = _decode_workspace(q.device, need)
-    wptr, wbytes = (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
-    return (B, R, cap, _ptr(n_dev), H, hkv, D, ldq, ldkv, seq_stride, wptr, wbytes)
-
-
-def _decode_batch_out(out, q):
-    B, R, H, D = q.shape
-    if out is None:
-        out = torch.empty((B * R, H * D), dtype=q.dtype, device=q.device)
-    assert out.dtype == q.dtype and out.shape == (B * R, H * D) and out.stride(1) == 1
-    return out, out.stride(0) if B * R > 1 else H * D
+    return _attn_decode(False, None, q, kv_cache, kv_scale, n_keys, causal, softmax_scale, out, workspace, (scale0, scale1, row_sel, tiled))
 
 
 @_on_device
@@ -835,14 +846,7 @@ def attn_decode_fp8kv_batch(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale: t
     padded: only stride(0) >= capacity * stride(1) is asked), kv_scale [2 * kv_heads] shared by the sequences, n_keys an int32 CUDA
     tensor [B] read on the device (None: every sequence holds ``capacity`` keys) -> [B * R, heads * 128].  Sequence b's rows are
     the bits ``attn_decode_fp8kv(q[b], kv_cache[b], ..., n_keys=n_keys[b])`` gives under the same plan."""
-    _need_cuda(q, kv_cache, kv_scale, out, workspace, n_keys)
-    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, torch.float8_e4m3fn)
-    out, ldo = _decode_batch_out(out, q)
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    call("mq_attn_decode_fp8kv_batch", q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq,
-         kv_scale.data_ptr(), float(softmax_scale), 1 if causal else 0, out.data_ptr(), ldo, wptr, wbytes, _stream())
-    return out
+    return _attn_decode(True, True, q, kv_cache, kv_scale, n_keys, causal, softmax_scale, out, workspace)
 
 
 @_on_device
@@ -850,14 +854,7 @@ def attn_decode_batch(q: torch.Tensor, kv_cache: torch.Tensor, n_keys: torch.Ten
                       softmax_scale: float = None, out: torch.Tensor = None, workspace: torch.Tensor = None) -> torch.Tensor:
     """``attn_decode_fp8kv_batch`` over 16-bit caches (``mq_attn_decode_batch``): kv_cache [B, capacity, 2 * kv_heads, 128] in q's
     dtype, no scales."""
-    _need_cuda(q, kv_cache, out, workspace, n_keys)
-    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, None, n_keys, workspace, q.dtype)
-    out, ldo = _decode_batch_out(out, q)
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    call("mq_attn_decode_batch", q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq,
-         float(softmax_scale), 1 if causal else 0, out.data_ptr(), ldo, wptr, wbytes, _stream())
-    return out
+    return _attn_decode(True, False, q, kv_cache, None, n_keys, causal, softmax_scale, out, workspace)
 
 
 @_on_device
@@ -868,101 +865,39 @@ def attn_decode_quant_i8_batch(q: torch.Tensor, kv_cache: torch.Tensor, kv_scale
     """``attn_decode_quant_i8`` for B sequences (``mq_attn_decode_fp8kv_quant_i8_batch``; kv_scale = None with caches of q's dtype:
     ``mq_attn_decode_quant_i8_batch``): the int8 activations ``quantize_act_i8`` would produce from the [B * R, heads * 128] output of
     the unfused batched call under the same plan, row-major or a ``TiledAct`` of B * R rows; row_sel: uint8 [B * R]."""
-    _need_cuda(q, kv_cache, kv_scale, row_sel, out, workspace, n_keys)
-    fp8 = kv_cache.dtype == torch.float8_e4m3fn and kv_scale is not None
-    assert fp8 or (kv_scale is None and kv_cache.dtype == q.dtype), \
-        f"kv_cache / kv_scale: float8_e4m3fn caches with their kv_scale, or caches of q's dtype ({q.dtype}) with kv_scale = None " \
-        f"(got {kv_cache.dtype}, kv_scale {'given' if kv_scale is not None else 'None'})"
-    B, R, T, n_dev, H, hkv, D, ldq, ldkv, seq, wptr, wbytes = _decode_batch_args(q, kv_cache, kv_scale, n_keys, workspace, kv_cache.dtype)
-    out, optr, K_pad, ldo = _out_act(out, tiled, B * R, H * D, q.device)
-    if softmax_scale is None:
-        softmax_scale = D ** -0.5
-    head = (q.data_ptr(), dtype_code(q.dtype), B, R, T, n_dev, H, hkv, D, ldq, kv_cache.data_ptr(), ldkv, seq)
-    tail = (float(softmax_scale), 1 if causal else 0, float(scale0), _second(scale0, scale1), _ptr(row_sel), optr, K_pad, ldo, wptr, wbytes,
-            _stream())
-    if fp8:
-        call("mq_attn_decode_fp8kv_quant_i8_batch", *head, kv_scale.data_ptr(), *tail)
-    else:
-        call("mq_attn_decode_quant_i8_batch", *head, *tail)
-    return out
+    return _attn_decode(True, None, q, kv_cache, kv_scale, n_keys, causal, softmax_scale, out, workspace, (scale0, scale1, row_sel, tiled))
 
 
-@_on_device
-def kv_append_rope_fp8_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv_scale: torch.Tensor, cos: torch.Tensor = None,
-                             sin: torch.Tensor = None, n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
-    """``kv_append_rope_fp8`` for B sequences in one launch (``mq_kv_append_rope_fp8_batch``): qkv [B * R, (heads + 2 * kv_heads) * D],
-    rows [b R, (b + 1) R) the R <= 8 new rows of sequence b, kv_cache [B, capacity, 2 * kv_heads, D] float8_e4m3fn; n_keys (the key
-    counts AFTER the append) and rope_delta: int32 CUDA tensors [B] read on the device, None = the capacity / no offset.  Per
-    sequence the bits and bytes of the single-sequence call.  Returns qkv."""
-    assert kv_scale is not None
-    return _kv_append_batch(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, torch.float8_e4m3fn)
-
-
-@_on_device
-def kv_append_rope_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, cos: torch.Tensor = None, sin: torch.Tensor = None,
-                         n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
-    """``kv_append_rope_fp8_batch`` into 16-bit caches (``mq_kv_append_rope_batch``): kv_cache [B, capacity, 2 * kv_heads, D] in qkv's
-    dtype, no scales."""
-    return _kv_append_batch(qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta, qkv.dtype)
-
-
-def _kv_append_batch(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, storage):
-    _need_cuda(qkv, kv_cache, kv_scale, cos, sin, n_keys, rope_delta)
-    B, cap, H2, D, ldkv, seq = _batch_cache(kv_cache, storage)
+def _kv_append(batched: bool, fp8: bool, qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta):
+    """The four append ops: the checks, the device integers and the call.  batched: qkv [B * R, ...] into caches [B, capacity, ...]
+    with B counts and B offsets, else qkv [R, ...] into one cache, seen as a batch of one.  fp8: an e4m3 cache with kv_scale, or one
+    of qkv's dtype without."""
+    is_t = lambda v: v if isinstance(v, torch.Tensor) else None
+    _need_cuda(qkv, kv_cache, kv_scale, cos, sin, is_t(n_keys), is_t(rope_delta))
+    B, cap, H2, D, ldkv, seq, T, n_dev = _cache_and_count(kv_cache, n_keys, batched, _E4M3 if fp8 else qkv.dtype)
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (heads + H2) * D and qkv.shape[0] % B == 0, \
-        f"qkv must be [B * R, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}] with B = {B} (got {tuple(qkv.shape)})"
+        f"qkv must be [{'B * R' if batched else 'R'}, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}]" \
+        f"{f' with B = {B}' if batched else ''} (got {tuple(qkv.shape)})"
     R = qkv.shape[0] // B
-    if kv_scale is not None:
+    if fp8:
+        assert kv_scale is not None
         _check_kv_scale(kv_scale, H2 // 2)
-    n_dev, d_dev = _batch_counts(n_keys, B, "n_keys"), _batch_counts(rope_delta, B, "rope_delta")
     assert (cos is None) == (sin is None), "cos and sin: both or neither"
     rows = 0
     if cos is not None:
         assert cos.dtype == qkv.dtype == sin.dtype and cos.dim() == 2 and cos.shape[1] == D and cos.shape == sin.shape
         assert cos.is_contiguous() and sin.is_contiguous()
         rows = cos.shape[0]
-    else:
-        d_dev = None
-    args = (qkv.data_ptr(), dtype_code(qkv.dtype), B, R, cap, _ptr(n_dev), _ptr(d_dev), heads, H2 // 2, D,
-            qkv.stride(0) if B * R > 1 else qkv.shape[1], _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(), ldkv, seq)
-    if kv_scale is not None:
-        call("mq_kv_append_rope_fp8_batch", *args, kv_scale.data_ptr(), _stream())
-    else:
-        call("mq_kv_append_rope_batch", *args, _stream())
+    d_dev = _device_counts(rope_delta, B, "rope_delta") if batched else rope_delta      # a batch takes no host-side integers
+    if cos is None or (not isinstance(d_dev, torch.Tensor) and not d_dev):
+        d_dev = None                                                   # no table, or a host-side 0: nothing to offset
+    elif not batched:
+        d_dev = _device_int(d_dev, "rope_delta", qkv.device)
+    call("mq_kv_append_rope" + ("_fp8" if fp8 else "") + ("_batch" if batched else ""),
+         qkv.data_ptr(), dtype_code(qkv.dtype), *((B,) if batched else ()), R, T, _ptr(n_dev), _ptr(d_dev), heads, H2 // 2, D,
+         qkv.stride(0) if B * R > 1 else qkv.shape[1], _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(), ldkv, *((seq,) if batched else ()),
+         *((kv_scale.data_ptr(),) if fp8 else ()), _stream())
     return qkv
-
-
-@_on_device
-def embed_gather_batch(table: torch.Tensor, ids: torch.Tensor, *, out: torch.Tensor = None, id_log: torch.Tensor = None,
-                       n_keys: torch.Tensor = None) -> torch.Tensor:
-    """``embed_gather`` for B <= 8 sequences of one new row each (``mq_embed_gather_batch``): ids int32 [B] on the device -> [B, dim],
-    out[b] = table[clamp(ids[b])].  id_log: int32 [B, log_rows] (rows may be padded); the clamped id of sequence b goes to
-    id_log[b, n_b - 1], n_b = clamp(n_keys[b], 1, log_rows) for an int32 CUDA tensor [B], log_rows for None."""
-    _need_cuda(table, ids, out, id_log, n_keys)
-    vocab, dim = table.shape
-    assert table.stride(1) == 1 and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
-    B = ids.shape[0]
-    if out is None:
-        out = torch.empty((B, dim), dtype=table.dtype, device=table.device)
-    assert out.dtype == table.dtype and out.shape == (B, dim) and out.stride(1) == 1
-    ld_log = log_rows = 0
-    if id_log is not None:
-        assert id_log.dtype == torch.int32 and id_log.dim() == 2 and id_log.shape[0] == B and id_log.stride(1) == 1
-        log_rows = id_log.shape[1]
-        ld_log = id_log.stride(0) if B > 1 else log_rows
-    n_dev = _batch_counts(n_keys, B, "n_keys")
-    call("mq_embed_gather_batch", table.data_ptr(), dtype_code(table.dtype), vocab, dim, table.stride(0) if vocab > 1 else dim,
-         ids.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1 else dim, _ptr(id_log), ld_log, log_rows, _ptr(n_dev), _stream())
-    return out
-
-
-def _device_int(v, name: str, device) -> Optional[torch.Tensor]:
-    """A device-side integer argument: an int32 CUDA tensor of one element as it is, a Python int as a fresh one (a fill on the current
-    stream: keep a tensor of your own for a step that must not allocate), None as None."""
-    if v is None or isinstance(v, torch.Tensor):
-        assert v is None or (v.dtype == torch.int32 and v.numel() == 1 and v.is_cuda), f"{name}: an int or an int32 CUDA tensor of one element"
-        return v
-    return torch.full((1,), int(v), dtype=torch.int32, device=device)
 
 
 @_on_device
@@ -976,7 +911,7 @@ def kv_append_rope_fp8(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv
     token t = n - R + r and uses row clamp(t + rope_delta, 0, rows - 1) of cos / sin [rows, D] (qkv's dtype, contiguous);
     rope_delta: an int or an int32 CUDA tensor of one element (HF Qwen2-VL's ``rope_deltas``), default 0.  cos = sin = None: append
     only.  With both integers on the device a captured step replays while the cache grows.  Returns qkv."""
-    return _kv_append(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, torch.float8_e4m3fn)
+    return _kv_append(False, True, qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta)
 
 
 @_on_device
@@ -986,42 +921,25 @@ def kv_append_rope(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, cos: t
     [n - R, n) receive the BITS of the rotated K columns and of the V columns -- nothing is quantised, there are no scales.  What
     ``attn_decode`` reads next.  Every other argument as there.  Returns qkv."""
     assert kv_cache.dtype == qkv.dtype, f"kv_cache must have qkv's dtype {qkv.dtype} (got {kv_cache.dtype}); an e4m3 cache: kv_append_rope_fp8"
-    return _kv_append(qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta, qkv.dtype)
+    return _kv_append(False, False, qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta)
 
 
-def _kv_append(qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta, storage):
-    """The two append entry points: the checks, the device integers and the call.  storage: the cache's dtype."""
-    is_t = lambda v: v if isinstance(v, torch.Tensor) else None
-    _need_cuda(qkv, kv_cache, kv_scale, cos, sin, is_t(n_keys), is_t(rope_delta))
-    cap, H2, D = kv_cache.shape
-    assert H2 % 2 == 0 and kv_cache.dtype == storage and kv_cache.stride(2) == 1 and kv_cache.stride(1) == D
-    hkv = H2 // 2
-    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (heads + H2) * D, \
-        f"qkv must be [R, (heads + 2 * kv_heads) * head_dim = {(heads + H2) * D}] (got {tuple(qkv.shape)})"
-    R = qkv.shape[0]
-    if kv_scale is not None:
-        _check_kv_scale(kv_scale, hkv)
-    if isinstance(n_keys, torch.Tensor):
-        T, n_dev = cap, _device_int(n_keys, "n_keys", qkv.device)
-    else:
-        T, n_dev = (cap if n_keys is None else int(n_keys)), None
-        assert T <= cap, f"n_keys = {T} exceeds the cache's capacity {cap}"
-    assert (cos is None) == (sin is None), "cos and sin: both or neither"
-    rows = 0
-    if cos is not None:
-        assert cos.dtype == qkv.dtype == sin.dtype and cos.dim() == 2 and cos.shape[1] == D and cos.shape == sin.shape
-        assert cos.is_contiguous() and sin.is_contiguous()
-        rows = cos.shape[0]
-    if cos is None or (not isinstance(rope_delta, torch.Tensor) and not rope_delta):
-        rope_delta = None                                              # no table, or a host-side 0: nothing to offset
-    d_dev = _device_int(rope_delta, "rope_delta", qkv.device)
-    args = (qkv.data_ptr(), dtype_code(qkv.dtype), R, T, _ptr(n_dev), _ptr(d_dev), heads, hkv, D, qkv.stride(0) if R > 1 else qkv.shape[1],
-            _ptr(cos), _ptr(sin), rows, kv_cache.data_ptr(), kv_cache.stride(0) if cap > 1 else H2 * D)
-    if storage == torch.float8_e4m3fn:
-        call("mq_kv_append_rope_fp8", *args, kv_scale.data_ptr(), _stream())
-    else:
-        call("mq_kv_append_rope", *args, _stream())
-    return qkv
+@_on_device
+def kv_append_rope_fp8_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, kv_scale: torch.Tensor, cos: torch.Tensor = None,
+                             sin: torch.Tensor = None, n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
+    """``kv_append_rope_fp8`` for B sequences in one launch (``mq_kv_append_rope_fp8_batch``): qkv [B * R, (heads + 2 * kv_heads) * D],
+    rows [b R, (b + 1) R) the R <= 8 new rows of sequence b, kv_cache [B, capacity, 2 * kv_heads, D] float8_e4m3fn; n_keys (the key
+    counts AFTER the append) and rope_delta: int32 CUDA tensors [B] read on the device, None = the capacity / no offset.  Per
+    sequence the bits and bytes of the single-sequence call.  Returns qkv."""
+    return _kv_append(True, True, qkv, heads, kv_cache, kv_scale, cos, sin, n_keys, rope_delta)
+
+
+@_on_device
+def kv_append_rope_batch(qkv: torch.Tensor, heads: int, kv_cache: torch.Tensor, cos: torch.Tensor = None, sin: torch.Tensor = None,
+                         n_keys: torch.Tensor = None, rope_delta: torch.Tensor = None) -> torch.Tensor:
+    """``kv_append_rope_fp8_batch`` into 16-bit caches (``mq_kv_append_rope_batch``): kv_cache [B, capacity, 2 * kv_heads, D] in qkv's
+    dtype, no scales."""
+    return _kv_append(True, False, qkv, heads, kv_cache, None, cos, sin, n_keys, rope_delta)
 
 
 def kv_scale_from_absmax(kv: torch.Tensor) -> torch.Tensor:

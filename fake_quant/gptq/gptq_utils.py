@@ -102,7 +102,8 @@ class GPTQ:
                 W[:, i2:] -= E1 @ Hinv[i1:i2, i2:]
         # --w_groupsize: every group's (scale, zero point) is KEPT (the reference's quantizer remembers the last group only,
         # gptq_utils.py:263-273); with contiguous groups -- no activation ordering -- they are what the integer backend needs
-        # (mq_gemm_w4a8_wgroupscale): quantizer.group_scales / group_zeros [rows, groups], quantizer.groupsize
+        # (mq_gemm_w4a8_wgroupscale; with --w_asym the zero points feed mq_gemm_w4a8_wgroupscale_asym):
+        # quantizer.group_scales / group_zeros [rows, groups], quantizer.groupsize
         group_scales, group_zeros = [], []
         for i1 in ([] if fused else range(0, self.columns, blocksize)):
             i2 = min(i1 + blocksize, self.columns)

@@ -385,6 +385,8 @@ class ActQuantWrapper(torch.nn.Module):
         mode = "static" if qz.static else "dynamic"
         if getattr(wq, "group_scales", None) is not None:
             mode += ", weight groups of %d" % wq.groupsize
+            if not getattr(wq, "sym", False):
+                mode += ", asymmetric"
         return "W%dA%d integer (%s)" % (wq.bits, qz.bits, mode)
 
     def _simulated_because(self) -> str:
@@ -419,8 +421,9 @@ class ActQuantWrapper(torch.nn.Module):
         return ""
 
     def _weight_groups_because(self, wq) -> str:
-        """--w_groupsize on the integer path (mq_gemm_w4a8_wgroupscale): contiguous groups of 64 or a multiple of 128 input
-        channels, symmetric levels, no split column; static, dynamic per-token symmetric or same-size group-wise activations."""
+        """--w_groupsize on the integer path (mq_gemm_w4a8_wgroupscale, with --w_asym mq_gemm_w4a8_wgroupscale_asym): contiguous groups
+        of 64 or a multiple of 128 input channels, no split column; static, dynamic per-token symmetric or same-size group-wise
+        activations."""
         qz = self.quantizer
         g = int(wq.groupsize)
         if getattr(wq, "group_scales", None) is None:
@@ -432,7 +435,12 @@ class ActQuantWrapper(torch.nn.Module):
             if (not qz.static) and getattr(qz, "groupsize", -1) > 0:
                 return "--act_order weight groups with group-wise activations (the activation groups would follow the permutation)"
         if not getattr(wq, "sym", False):
-            return "asymmetric weights with --w_groupsize"
+            # --w_asym: one zero point per (channel, group) next to the scale (the solver and the group-wise RTN record both)
+            if getattr(wq, "group_zeros", None) is None:
+                return "asymmetric weights with --w_groupsize: group zero points not recorded"
+            if wq.bits == 8 and g > 512:
+                # |sum_{k in g} a (q - z)| <= g 128 255 must stay an exact float (< 2^24) for the kernel's conversion
+                return "asymmetric 8-bit weight groups of %d (a group's integer sum passes 2^24 above 512)" % g
         if self.split:
             return "--w_groupsize with the split column"
         _, wmod = self._weight_module()
@@ -521,8 +529,12 @@ class ActQuantWrapper(torch.nn.Module):
             name, wmod = self._weight_module()
             wq = self.weight_quantizers.get(name)
             width = wmod.weight.shape[1] if wmod.weight.dim() == 2 else 0
+            # (asymmetric weights come through only as weight groups of the same size with their zero points recorded: the integer
+            #  correction of mq_gemm_w4a8_wgroupscale_asym; _weight_groups_because has the remaining conditions)
+            w_ok = wq is not None and (bool(getattr(wq, "sym", False)) or (getattr(wq, "group_zeros", None) is not None and getattr(qz, "sym", False)
+                                                                          and int(getattr(wq, "groupsize", -1) or -1) == g))
             return (not self.split and (g == 64 or g % 128 == 0) and g <= 1024
-                    and (g & (g - 1)) == 0 and width > 0 and width % g == 0 and wq is not None and bool(getattr(wq, "sym", False)))
+                    and (g & (g - 1)) == 0 and width > 0 and width % g == 0 and w_ok)
         # (per-tensor ranges on half / bf16 activations: the reference keeps range, scale, zero point, x / scale and the
         #  level sum in x's dtype -- quant_utils.py:214-231, ``torch.tensor(0).to(x)``, the int64 maxq does not promote -- and
         #  mq_quantize_act_range_i8 rounds exactly there; goldens wrapper_dynpt16_* from the reference on fp16 / bf16)
@@ -543,6 +555,7 @@ class ActQuantWrapper(torch.nn.Module):
             scale = scale.expand(W2.shape[0]).contiguous()
         w_shift = None
         w_groups = None
+        group_shift = None
         col_perm = None
         if getattr(wq, "group_scales", None) is not None:
             # --w_groupsize: one scale per (channel, group of g consecutive input channels); levels on each group's own grid
@@ -555,9 +568,19 @@ class ActQuantWrapper(torch.nn.Module):
                 assert col_perm.numel() == W2.shape[1]
                 W2 = W2.index_select(1, col_perm)
             half = 1 << (wq.bits - 1)
-            levels = torch.round(W2.float().reshape(W2.shape[0], -1, g) / gs[:, :, None]).clamp(-half, half - 1)
+            diff = torch.round(W2.float().reshape(W2.shape[0], -1, g) / gs[:, :, None])
+            if getattr(wq, "sym", False):
+                levels = diff.clamp(-half, half - 1)
+                w_groups = (gs.t().contiguous(), g)                                      # [K / g, N] as the kernel reads it
+            else:
+                # --w_asym per group: W~ = s_g (q - z_g), rint(W~ / s_g) = q - z_g; stored level = q - 2^(b-1), and the kernel gets the
+                # integer zero offsets d_g = 2^(b-1) - z_g next to the scales
+                gz = torch.round(wq.group_zeros.to(device=device, dtype=torch.float32))  # [N, K / g]
+                assert gz.shape == gs.shape, "group zero points do not match the group scales"
+                levels = (diff + (gz - float(half))[:, :, None]).clamp(-half, half - 1)
+                w_groups = (gs.t().contiguous(), g, (float(half) - gz).t().to(torch.int16).contiguous())
+                group_shift = (gs * (float(half) - gz)).repeat_interleave(g, dim=1)      # per element, for the grid check below
             levels = levels.reshape(W2.shape).to(torch.int8)
-            w_groups = (gs.t().contiguous(), g)                                          # [K / g, N] as the kernel reads it
             scale = gs.repeat_interleave(g, dim=1)                                       # per element, for the grid check below
         elif getattr(wq, "sym", False):
             levels = ops.weight_levels(W2, scale, wq.bits)
@@ -578,6 +601,8 @@ class ActQuantWrapper(torch.nn.Module):
         # a foreign grid, at most a few 1e-2 for half-precision roundings of scale * level, 0 in fp32)
         sc2 = scale if scale.dim() == 2 else scale[:, None]
         grid_w = levels.float() * sc2 if w_shift is None else levels.float() * sc2 + w_shift[:, None]
+        if group_shift is not None:
+            grid_w = grid_w + group_shift
         dev_steps = ((grid_w - W2.float()).abs() / sc2).mean()
         if float(dev_steps) > 0.12:
             raise RuntimeError(f"ActQuantWrapper: weights of '{name}' are not on the attached quantizer's grid "
@@ -845,11 +870,14 @@ class SiblingGroup:
         if any(p["s0"] != p0["s0"] or p["s1"] != p0["s1"] or p["bits"] != p0["bits"] or p["dynamic"] is not None
                or p["w_shift"] is not None or p["levels"].shape[1] != p0["levels"].shape[1]
                or (p["w_groups"] is None) != (p0["w_groups"] is None) or p["col_perm"] is not None
-               or (p["w_groups"] is not None and p["w_groups"][1] != p0["w_groups"][1]) for p in parts):
+               or (p["w_groups"] is not None and (p["w_groups"][1] != p0["w_groups"][1] or len(p["w_groups"]) != len(p0["w_groups"])))
+               for p in parts):
             return False
         w_groups = None
         if p0["w_groups"] is not None:                      # --w_groupsize: the members' [groups, channels] scale tables side by side
             w_groups = (torch.cat([p["w_groups"][0] for p in parts], dim=1).contiguous(), p0["w_groups"][1])
+            if len(p0["w_groups"]) > 2:                     # ... and with --w_asym their zero-offset tables
+                w_groups += (torch.cat([p["w_groups"][2] for p in parts], dim=1).contiguous(),)
         bias = None
         if any(p["bias"] is not None for p in parts):
             bias = torch.cat([p["bias"].float() if p["bias"] is not None

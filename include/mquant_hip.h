@@ -727,6 +727,28 @@ int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w, int w_bit
                              const uint8_t *row_sel, const float *s_x_rows, const float *s_x_groups,
                              const float *bias, void *out, int out_dtype, long ldo, void *stream);
 
+/* ... for ASYMMETRIC weight groups (--w_groupsize g --w_asym: the solver runs WeightQuantizer.find_params with sym = False on every
+ * group, reference fake_quant/gptq/gptq_utils.py:263-275, fake_quant/quant_utils.py:446-509, asym_quant_dequant :27-40):
+ *   W~[n][k] = s_g[n] (q - z_g[n]),  q in 0 .. 2^b - 1,  z_g[n] = round(-xmin / s) an integer in 0 .. 2^b - 1.
+ * The image stores q - 2^(b-1) (as for per-channel --w_asym).  With the group's zero offset d_g[n] = 2^(b-1) - z_g[n]
+ * (w_zero_offsets[g * N + n], int16: -7 .. 8 for int4, -127 .. 128 for int8) and the activation group sums r_g[m] = sum_{k in g} a[m][k]
+ * (a_group_sums[m * n_groups + g], from mq_act_group_rowsum_i32 over the same levels)
+ *   acc'_g[m][n] = acc_g[m][n] + d_g[n] r_g[m]            (exact integers: = sum_{k in g} a[m][k] (q - z))
+ *   y[m][n] = (sum_g ((float(acc'_g) * s_x_groups[m][g]) * s_w_groups[g][n])) * s_x(m) + bias[n]
+ * -- mq_gemm_w4a8_wgroupscale's formula with acc' in place of acc: the same ascending group order, roundings and s_x(m) cases.  Both
+ * tables are required; int8 weights: groups of at most 512 (float(acc') stays exact), larger ones are MQ_EUNSUPPORTED. */
+int mq_gemm_w4a8_wgroupscale_asym(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
+                                  const float *s_w_groups, const int16_t *w_zero_offsets, const int32_t *a_group_sums,
+                                  long n_groups, int group_k, float s_x0, float s_x1, const uint8_t *row_sel,
+                                  const float *s_x_rows, const float *s_x_groups, const float *bias, void *out,
+                                  int out_dtype, long ldo, void *stream);
+
+/* The activation group sums of the call above: out[m * n_groups + g] = sum of a[m][g * group_k .. (g + 1) * group_k - 1], exact int32
+ * (the row factor of the zero points of asymmetric weight groups, reference quant_utils.py:446-509 per group as gptq_utils.py:263-275
+ * runs it).  a: [M, K_pad] int8 levels with lda bytes per row or lda = MQ_LD_TILED; group_k: 64 or a multiple of 128;
+ * n_groups * group_k <= K_pad -- groups that lie in the zero padding sum to 0.  One launch. */
+int mq_act_group_rowsum_i32(const int8_t *a, long lda, long M, long K_pad, int group_k, long n_groups, int32_t *out, void *stream);
+
 /* Scaled row sums of the int8 activation levels, for ASYMMETRIC weights (--w_asym; WeightQuantizer with
  * sym = False, quant_utils.py:446-509).  With the weight levels stored as q - 2^(b-1) the fake-quantized
  * weight is s_w[n] (stored + 2^(b-1) - z_w[n]); the zero points come back through the rank-1 epilogue term

@@ -92,6 +92,12 @@ struct GemmArgs {
     int kq = 0, kr = 0;              // k units per split: split s owns kq (+1 if s < kr) units from s*kq + min(s, kr)
     // XCD grouping of the m-blocks (set_geometry): xm groups of mg = m_blocks / xm blocks each
     unsigned xm = 1, mg = 1, mag_xm = 0;
+    // ASYMMETRIC weight groups (--w_groupsize g --w_asym; find_params with sym = False per group, reference gptq/gptq_utils.py:263-275,
+    // quant_utils.py:446-509): the image holds q - 2^(b-1), wd_groups[g * N + n] = 2^(b-1) - z_g[n] and a_gsums[m * n_groups + g] =
+    // sum_{k in g} a[m][k] (mq_act_group_rowsum_i32); a group's accumulator becomes acc + d r -- an exact integer -- before its
+    // conversion.  (Last in the block: every member above keeps its offset.)
+    const int16_t *wd_groups = nullptr;
+    const int32_t *a_gsums = nullptr;
 };
 
 // The 8 XCDs have private L2s: whatever two XCDs both touch crosses the fabric twice.  Work ids are

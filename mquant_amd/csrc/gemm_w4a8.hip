@@ -46,9 +46,14 @@ int launch_gemm_skinny_wg(const GemmArgs &p, hipStream_t st);          // gemm_s
 // GROUPED (--a_groupsize): the int32 accumulators of one activation group (64 or a multiple of 128 k) are scaled by
 // the group's activation scale of their row and added to fp32 accumulators in ascending group order; the epilogue
 // gets the float bits (GemmArgs::acc_float).  Exact integers inside a group, one fp32 rounding per group and row.
-template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int W_BITS, int EPI, int DMA_POS, bool GROUPED = false>
+// WASYM (GROUPED with weight-group scales): ASYMMETRIC weight groups (--w_groupsize g --w_asym; find_params with sym = False per group,
+// reference gptq/gptq_utils.py:263-275, quant_utils.py:446-509, asym_quant_dequant :27-40).  The image holds q - 2^(b-1); a group's
+// accumulator becomes acc + d_g[n] r_g[m] = sum_{k in g} a[m][k] (q - z) (GemmArgs::wd_groups, a_gsums) -- integers, exact -- and
+// is then converted and scaled like a symmetric group's.
+template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int W_BITS, int EPI, int DMA_POS, bool GROUPED = false, bool WASYM = false>
 __global__ __launch_bounds__(WARPS_M *WARPS_N * 64) void gemm_w4a8_kernel(GemmArgs p)
 {
+    static_assert(!WASYM || GROUPED, "the zero-point correction lives in the group fold");
     kernarg_warm<sizeof(GemmArgs), true>();
     constexpr int NWAVES = WARPS_M * WARPS_N;
     constexpr int TM = BM / WARPS_M / 16;          // activation fragments per wave
@@ -149,12 +154,20 @@ __global__ __launch_bounds__(WARPS_M *WARPS_N * 64) void gemm_w4a8_kernel(GemmAr
             float sg = p.sx_groups ? p.sx_groups[row * p.n_groups + gi] : 1.0f;   // (weight groups alone: the row scale waits in the epilogue)
             if (W_BITS == 4) sg = sg * 0.0625f;                // the int4 levels sit in the high nibble: exact rescale
             const float sh = (p.shift_groups && !tail) ? p.shift_groups[row * p.n_groups + gi] : 0.0f;
+            // asymmetric weight groups: the row's group sum, in the accumulators' unit (int4 levels sit in the high nibble).  Like the
+            // shift term it is no accumulator product: the zero-padded tail must not add the last real group's a second time.
+            int rg = 0;
+            if (WASYM && !tail) rg = p.a_gsums[row * p.n_groups + gi] * (W_BITS == 4 ? 16 : 1);
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
                 // D layout: register r of the tile = channel 16 (nt0 + wn TN + i) + 4 (lane >> 4) + r
                 const long nb = (nt0 + wn * TN + i) * 16 + (lane >> 4) * 4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
+                    if (WASYM) {                               // acc' = acc + d r: |acc'| <= group_k 128 (2^b - 1) (x 16 for int4), an exact float
+                        const long nn = nb + r < p.N ? nb + r : p.N - 1;
+                        acc[i][j][r] += (int)p.wd_groups[gi * p.N + nn] * rg;
+                    }
                     float t = (float)acc[i][j][r] * sg;
                     if (p.sw_groups) {                         // weight-group scale of (group, channel): one more rounding
                         const long nn = nb + r < p.N ? nb + r : p.N - 1;
@@ -492,12 +505,12 @@ static int launch_gemm_pipe(const GemmArgs &p, hipStream_t st)
     return finish_splitk<EPI>(check_launch("gemm_w4a8_pipe"), p, st);
 }
 
-template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int W_BITS, int EPI, int DMA_POS = 1, bool GROUPED = false>
+template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int W_BITS, int EPI, int DMA_POS = 1, bool GROUPED = false, bool WASYM = false>
 static int launch_gemm(const GemmArgs &p, hipStream_t st)
 {
     constexpr int PIECES = (BM / 16) * 2 + ((W_BITS == 4) ? (BN / 16) : (BN / 16) * 2);
     constexpr int SMEM = STAGES * PIECES * 1024;
-    auto kern = gemm_w4a8_kernel<BM, BN, WARPS_M, WARPS_N, STAGES, W_BITS, EPI, DMA_POS, GROUPED>;
+    auto kern = gemm_w4a8_kernel<BM, BN, WARPS_M, WARPS_N, STAGES, W_BITS, EPI, DMA_POS, GROUPED, WASYM>;
     {
         const int rc = ensure_dynamic_lds((const void *)kern, SMEM);
         if (rc != MQ_OK) return rc;
@@ -699,6 +712,8 @@ struct GemmCall {
     const uint8_t *row_sel = nullptr;
     const float *s_w = nullptr, *bias = nullptr, *x0 = nullptr, *w0 = nullptr, *x1 = nullptr, *w1 = nullptr, *sx_vec = nullptr;
     const float *sx_groups = nullptr, *shift_groups = nullptr, *wsum_groups = nullptr, *sw_groups = nullptr;
+    const int16_t *wd_groups = nullptr;   // asymmetric weight groups: zero offsets and activation group sums (both or neither)
+    const int32_t *a_gsums = nullptr;
     long n_groups = 0;
     int group_k = 0;
     const void *residual = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
@@ -781,6 +796,17 @@ static int gemm_common(const GemmCall &c)
         p.shift_groups = c.shift_groups; p.wsum_groups = c.wsum_groups;
         p.splits = 1; p.partial = nullptr;
         p.par_ok = al16(c.s_w) && al16(c.bias) && al16(c.w0);
+        if (c.wd_groups) {
+            // asymmetric weight groups: the round-1 kernel, whose fold CONVERTS the group's integer -- exact for every group size the
+            // entry point lets through.  The wave-specialised fold reads a group's sum out of the magic bias without a conversion, which
+            // is exact only while |sum| < 2^18 (int4) / 2^22 (int8): levels q - z span +-15 / +-255, so that proof ends at groups of 128
+            // (128 * 128 * 15 < 2^18 < 256 * 128 * 15) and its tiles do not serve this mode; a forced tile is ignored like a forced
+            // tile outside the wave-specialised set is for the symmetric call.
+            p.wd_groups = c.wd_groups; p.a_gsums = c.a_gsums;
+            return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) {
+                return launch_gemm<128, 128, 2, 4, 3, decltype(wb)::value, decltype(e)::value, 1, true, true>(p, st);
+            });
+        }
         if (a_tiled && !c.shift_groups && (!c.sw_groups || (N % 4 == 0 && ((uintptr_t)c.sw_groups) % 16 == 0)) && g_force_tile != TILE_SYM_128x128) {
             // symmetric group scales (weights, activations or both) on tiled activations, groups of 64 or of whole k-steps: the fold rides in the
             // wave-specialised 16x16x64 kernels (weight groups of 128: 1.8-2.4 x the per-channel GEMM of the shape, profiles/r5_group_gemm_ws_fold.txt,
@@ -998,6 +1024,32 @@ extern "C" int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w
     mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
     c.s_x0 = unit ? 1.0f : s_x0; c.s_x1 = unit ? 1.0f : s_x1; c.row_sel = unit ? nullptr : row_sel; c.sx_vec = s_x_groups ? nullptr : s_x_rows;
     c.sx_groups = s_x_groups; c.sw_groups = s_w_groups; c.n_groups = n_groups; c.group_k = group_k; c.bias = bias;
+    return mq::gemm_common(c);
+}
+
+extern "C" int mq_gemm_w4a8_wgroupscale_asym(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
+                                             const float *s_w_groups, const int16_t *w_zero_offsets, const int32_t *a_group_sums,
+                                             long n_groups, int group_k, float s_x0, float s_x1, const uint8_t *row_sel,
+                                             const float *s_x_rows, const float *s_x_groups, const float *bias, void *out,
+                                             int out_dtype, long ldo, void *stream)
+{
+    if (const int rc = mq::check_float_dtype(__func__, out_dtype)) return rc;
+    if (M == 0 || N == 0) return MQ_OK;
+    if (!s_w_groups || n_groups <= 0) return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale_asym: s_w_groups is required");
+    if (!w_zero_offsets || !a_group_sums)
+        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale_asym: w_zero_offsets and a_group_sums are required (symmetric groups: mq_gemm_w4a8_wgroupscale)");
+    if (const int rc = mq::check_groups_cover(__func__, n_groups, group_k, K_pad)) return rc;
+    if (s_x_groups && (s_x_rows || row_sel))
+        return mq::fail(MQ_EINVAL, "mq_gemm_w4a8_wgroupscale_asym: group-wise activation scales exclude per-row / per-token-type scales");
+    // float(acc') must be exact: |acc'| <= group_k * 128 * 255 stays below 2^24 up to groups of 512 (int4: 16 x group_k * 128 * 15, a
+    // multiple of 16 -- exact for every group size)
+    if (w_bits == 8 && group_k > 512)
+        return mq::fail(MQ_EUNSUPPORTED, "mq_gemm_w4a8_wgroupscale_asym: int8 weight groups of %d (a group's sum of 255 x 128 products passes 2^24 above 512)", group_k);
+    const bool unit = s_x_groups || s_x_rows;           // the row scale is elsewhere: x 1.0 in the epilogue is exact
+    mq::GemmCall c = mq::gemm_call(a, lda, w, w_bits, M, N, K_pad, out, out_dtype, ldo, stream);
+    c.s_x0 = unit ? 1.0f : s_x0; c.s_x1 = unit ? 1.0f : s_x1; c.row_sel = unit ? nullptr : row_sel; c.sx_vec = s_x_groups ? nullptr : s_x_rows;
+    c.sx_groups = s_x_groups; c.sw_groups = s_w_groups; c.wd_groups = w_zero_offsets; c.a_gsums = a_group_sums;
+    c.n_groups = n_groups; c.group_k = group_k; c.bias = bias;
     return mq::gemm_common(c);
 }
 

@@ -44,6 +44,59 @@ __global__ __launch_bounds__(256) void act_rowsum_kernel(RsArgs p)
     }
 }
 
+// Group sums of the int8 activation levels, r_g[m] = sum_{k in g} a[m][k] as exact int32: the row factor of the integer correction
+// d_g[n] r_g[m] that carries the zero points of ASYMMETRIC WEIGHT GROUPS (--w_groupsize g --w_asym; WeightQuantizer.find_params with
+// sym = False per group, reference gptq/gptq_utils.py:263-275, quant_utils.py:446-509).  One wave per row, 16 bytes per lane per access;
+// LPG = group_k / 16 lanes share a group.  POW2 (LPG a power of two <= 64: groups of 64 .. 1024): the wave reads 1024 consecutive
+// levels at a time and every run of LPG lanes reduces its own group; otherwise the wave walks the row group by group.
+struct GrsArgs {
+    const int8_t *a;
+    long M, K_pad, lda, n_groups;
+    int group_k;
+    int32_t *out;
+};
+
+__device__ __forceinline__ int sum_levels16(const v4i v)
+{
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int w = v[j];
+        acc += (int)(signed char)(w & 0xff) + (int)(signed char)((w >> 8) & 0xff) + (int)(signed char)((w >> 16) & 0xff) + (w >> 24);
+    }
+    return acc;
+}
+
+template <bool POW2>
+__global__ __launch_bounds__(256) void act_group_rowsum_kernel(GrsArgs p)
+{
+    kernarg_warm<sizeof(GrsArgs)>();
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.M) return;                            // (whole waves leave: the shuffles below see full waves)
+    const int lpg = p.group_k >> 4;
+    int32_t *dst = p.out + row * p.n_groups;
+    if (POW2) {
+        for (long k0 = 0; k0 < p.K_pad; k0 += 1024) {
+            const long k = k0 + lane * 16L;
+            int acc = 0;
+            if (k < p.K_pad) acc = sum_levels16(*reinterpret_cast<const v4i *>(p.a + act_offset(row, k, p.K_pad, p.lda)));
+            for (int st = 1; st < lpg; st <<= 1) acc += __shfl_xor(acc, st, 64);
+            const long g = k / p.group_k;
+            if ((lane & (lpg - 1)) == 0 && k < p.K_pad && g < p.n_groups) dst[g] = acc;
+        }
+    } else {
+        for (long g = 0; g < p.n_groups; ++g) {
+            int acc = 0;
+            for (int c = lane; c < lpg; c += 64)
+                acc += sum_levels16(*reinterpret_cast<const v4i *>(p.a + act_offset(row, g * p.group_k + c * 16L, p.K_pad, p.lda)));
+#pragma unroll
+            for (int st = 1; st < 64; st <<= 1) acc += __shfl_xor(acc, st, 64);
+            if (lane == 0) dst[g] = acc;
+        }
+    }
+}
+
 // out[m][n] = cast(y32[m][n] + x[m] * w[n]): the THIRD rank-1 term of a layer that uses the split column, asymmetric weights and
 // asymmetric dynamic activations at once (the GEMM epilogue has two slots).  The GEMM runs with an fp32 output, so this pass
 // continues the epilogue's sum in fp32 and rounds to the output dtype once -- the same arithmetic a third slot would do.
@@ -90,6 +143,21 @@ extern "C" int mq_rank1_add_cast(const float *y32, long M, long N, long ldy, con
         hipLaunchKernelGGL(rank1_add_cast_kernel<decltype(dt)::value>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
         return check_launch("rank1_add_cast");
     });
+}
+
+extern "C" int mq_act_group_rowsum_i32(const int8_t *a, long lda, long M, long K_pad, int group_k, long n_groups, int32_t *out, void *stream)
+{
+    using namespace mq;
+    if (M == 0) return MQ_OK;
+    MQ_REQUIRE(a && out && M > 0 && K_pad > 0 && ((uintptr_t)out) % 4 == 0, "mq_act_group_rowsum_i32: bad shape");
+    if (const int rc = check_act_dest(__func__, a, K_pad, K_pad, lda, "bad lda / alignment")) return rc;
+    MQ_REQUIRE(group_k == 64 || (group_k > 0 && group_k % 128 == 0), "mq_act_group_rowsum_i32: group size %d (64 or a multiple of 128)", group_k);
+    MQ_REQUIRE(n_groups > 0 && n_groups * (long)group_k <= K_pad, "mq_act_group_rowsum_i32: %ld groups of %d exceed K_pad=%ld", n_groups, group_k, K_pad);
+    GrsArgs p{a, M, K_pad, lda, n_groups, group_k, out};
+    const bool pow2 = group_k <= 1024 && (group_k & (group_k - 1)) == 0;
+    if (pow2) hipLaunchKernelGGL(act_group_rowsum_kernel<true>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(act_group_rowsum_kernel<false>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch("act_group_rowsum_i32");
 }
 
 extern "C" int mq_act_rowsum_scaled(const int8_t *a, long lda, long M, long K_pad, float s_x0, float s_x1,

@@ -58,6 +58,7 @@ class Workspace:
     def __init__(self):
         self._a: Dict[Tuple[int, int, str], torch.Tensor] = {}
         self._x0: Dict[int, torch.Tensor] = {}
+        self._gsum: Dict[int, torch.Tensor] = {}            # int32 activation group sums (asymmetric weight groups)
         self._captured = set()          # ids of buffers handed out while a stream was capturing
         self._pinned = []               # outgrown buffers a graph may still replay into
         self._gen: Dict[Tuple[int, int, str], int] = {}     # hand-outs per key (debug: stale-handle check)
@@ -115,15 +116,20 @@ class Workspace:
     def x0(self, device, M: int) -> torch.Tensor:
         return self._grow(self._x0, device.index or 0, M, torch.float32, device)[:M]
 
+    def gsum(self, device, M: int, n_groups: int) -> torch.Tensor:
+        """int32 [M, n_groups] for ``mq_act_group_rowsum_i32``: like the activation image, written and read back to back on one stream."""
+        return self._grow(self._gsum, device.index or 0, M * n_groups, torch.int32, device)[: M * n_groups].view(M, n_groups)
+
     def nbytes(self) -> int:
         """Bytes held (live buffers + outgrown ones pinned by a graph)."""
-        bufs = list(self._a.values()) + list(self._x0.values()) + self._pinned
+        bufs = list(self._a.values()) + list(self._x0.values()) + list(self._gsum.values()) + self._pinned
         return sum(b.numel() * b.element_size() for b in bufs)
 
     def clear(self) -> None:
         """Drop every buffer (only when no captured graph will replay into them)."""
         self._a.clear()
         self._x0.clear()
+        self._gsum.clear()
         self._captured.clear()
         self._pinned.clear()
         self._views.clear()
@@ -140,7 +146,7 @@ class W4A8Linear:
                  had: Optional[HadamardSpec] = None, w0: Optional[torch.Tensor] = None,
                  in_features: Optional[int] = None, dynamic: Optional[dict] = None,
                  w_shift: Optional[torch.Tensor] = None, split_slice: bool = False,
-                 w_groups: Optional[Tuple[torch.Tensor, int]] = None, col_perm: Optional[torch.Tensor] = None):
+                 w_groups: Optional[tuple] = None, col_perm: Optional[torch.Tensor] = None):
         assert levels.is_cuda and levels.dtype == torch.int8 and levels.dim() == 2
         self.N, self.K = levels.shape
         self.K_pad = ops.ceil_to(self.K, 128)
@@ -160,12 +166,22 @@ class W4A8Linear:
         self.w_shift = None if w_shift is None else w_shift.reshape(-1).to(torch.float32).contiguous()
         #: group-wise WEIGHT scales (--w_groupsize; reference gptq/gptq_utils.py:263-273): (fp32 [K / g, N], g).  The GEMM is
         #: mq_gemm_w4a8_wgroupscale: exact int32 inside a group, the group's scale, fp32 across groups; s_w is unused.
+        #: ASYMMETRIC groups (--w_groupsize + --w_asym; find_params with sym = False per group, quant_utils.py:446-509): ``w_groups`` has a
+        #: third member, the zero offsets 2^(b-1) - z_g[n] as int16 [K / g, N]; levels are stored minus 2^(b-1).  One
+        #: mq_act_group_rowsum_i32 launch over the quantized levels, then mq_gemm_w4a8_wgroupscale_asym adds offset x group sum to
+        #: every group's integer accumulator.
         self.w_groups = None
+        self.w_group_offsets = None
         if w_groups is not None:
-            tbl, g = w_groups
+            tbl, g = w_groups[0], w_groups[1]
+            offs = w_groups[2] if len(w_groups) > 2 else None
             assert tbl.dtype == torch.float32 and tuple(tbl.shape) == (self.K // g, self.N) and self.K % g == 0
-            assert w0 is None and w_shift is None, "weight groups: no split column, symmetric levels"
+            assert w0 is None and w_shift is None, "weight groups: no split column, zero points per group (w_groups[2]), not per channel"
             self.w_groups = (tbl.contiguous(), int(g))
+            if offs is not None:
+                assert offs.dtype == torch.int16 and tuple(offs.shape) == tuple(tbl.shape) and offs.device == tbl.device
+                assert w_bits == 4 or g <= 512, "int8 asymmetric weight groups: at most 512 (float(group sum) must stay exact)"
+                self.w_group_offsets = offs.contiguous()
         #: --act_order with --w_groupsize (reference gptq/gptq_utils.py:228-233, 263-273): the weight image keeps the solver's column
         #: order (column j = input channel col_perm[j]; its groups are runs of those columns), so the activation columns are gathered
         #: the same way -- after the pad and the online Hadamard, in front of the quantizer (a gather of the fp tensor: elementwise
@@ -283,9 +299,7 @@ class W4A8Linear:
         if DEBUG_WORKSPACE:
             WORKSPACE.check_fresh(a)
         if self.w_groups is not None:
-            return ops.gemm_w4a8_wgroupscale(a, self.w_img, self.w_bits, self.N, self.w_groups[0], self.w_groups[1],
-                                             s_x0=self.s_x0, s_x1=self.s_x1, row_sel=row_sel, bias=self.bias,
-                                             out_dtype=out_dtype, out=out)
+            return self._gemm_wgroups(a, out_dtype, out, s_x0=self.s_x0, s_x1=self.s_x1, row_sel=row_sel)
         if self.w_shift is not None:
             xs = ops.act_rowsum_scaled(a, self.s_x0, self.s_x1, row_sel)
             if self.split:                   # --w_asym + --visual_split: both rank-1 slots
@@ -296,6 +310,16 @@ class W4A8Linear:
         return ops.gemm_w4a8(a, self.w_img, self.w_bits, self.N, self.s_x0, self.s_w,
                              s_x1=self.s_x1, row_sel=row_sel, bias=self.bias, x0=x0, w0=w0,
                              out_dtype=out_dtype, out=out)
+
+    def _gemm_wgroups(self, a, out_dtype: torch.dtype, out: Optional[torch.Tensor], **scales):
+        """The weight-group GEMM over the levels ``a``; ``scales``: the activation-scale arguments of the mode (static set(s), per-row or
+        per-group).  Asymmetric groups first take the group sums of the same levels (gathered ones under --act_order)."""
+        tbl, g = self.w_groups
+        if self.w_group_offsets is None:
+            return ops.gemm_w4a8_wgroupscale(a, self.w_img, self.w_bits, self.N, tbl, g, bias=self.bias, out_dtype=out_dtype, out=out, **scales)
+        sums = ops.act_group_rowsum(a, g, tbl.shape[0], out=WORKSPACE.gsum(self.w_img.device, ops._a_args(a)[2], tbl.shape[0]))
+        return ops.gemm_w4a8_wgroupscale_asym(a, self.w_img, self.w_bits, self.N, tbl, self.w_group_offsets, sums, g, bias=self.bias,
+                                              out_dtype=out_dtype, out=out, **scales)
 
     def act_in_store_ok(self, act: int) -> bool:
         """Whether ``gemm_act`` can run this layer: a plain static layer (no split column, rank-1 terms, groups or --act_order), tiled
@@ -360,8 +384,7 @@ class W4A8Linear:
             a, s_groups = ops.quantize_act_group_i8(x2, g, self.dynamic["bits"], self.dynamic["clip_ratio"], out=a)
             if self.w_groups is not None:        # ... and --w_groupsize of the same size: both scales per group
                 assert self.w_groups[1] == g
-                return ops.gemm_w4a8_wgroupscale(a, self.w_img, self.w_bits, self.N, self.w_groups[0], g, s_x_groups=s_groups,
-                                                 bias=self.bias, out_dtype=x2.dtype, out=out)
+                return self._gemm_wgroups(a, x2.dtype, out, s_x_groups=s_groups)
             return ops.gemm_w4a8_groupscale(a, self.w_img, self.w_bits, self.N, s_groups, g, self.s_w, bias=self.bias,
                                             out_dtype=x2.dtype, out=out)
         asym = self.w_colsum is not None
@@ -381,8 +404,7 @@ class W4A8Linear:
         if x0 is None:
             x0 = x0q
         if self.w_groups is not None:            # dynamic per-token symmetric activations x weight groups
-            return ops.gemm_w4a8_wgroupscale(a, self.w_img, self.w_bits, self.N, self.w_groups[0], self.w_groups[1],
-                                             s_x_rows=s_rows, bias=self.bias, out_dtype=x2.dtype, out=out)
+            return self._gemm_wgroups(a, x2.dtype, out, s_x_rows=s_rows)
         # the rank-1 epilogue terms (row factor, channel factor) of this layer, at most two
         terms = []
         if self.split:

@@ -1191,6 +1191,47 @@ def act_rowsum_scaled(a, s_x0: float = 1.0, s_x1: Optional[float] = None, row_se
 
 
 @_on_device
+def act_group_rowsum(a, group_k: int, n_groups: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum_{k in g} a[m][k] per row and group of ``group_k`` int8 activation levels, exact int32 [M, n_groups]
+    (``mq_act_group_rowsum_i32``): the row factor of the zero points of asymmetric weight groups."""
+    _need_cuda(a if not isinstance(a, TiledAct) else a.data, out)
+    aptr, lda, M, K_pad = _a_args(a)
+    dev = a.data.device if isinstance(a, TiledAct) else a.device
+    if out is None:
+        out = torch.empty((M, n_groups), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (M, n_groups)
+    call("mq_act_group_rowsum_i32", aptr, lda, M, K_pad, int(group_k), int(n_groups), out.data_ptr(), _stream())
+    return out
+
+
+@_on_device
+def gemm_w4a8_wgroupscale_asym(a, w_img: torch.Tensor, w_bits: int, N: int, s_w_groups: torch.Tensor, w_zero_offsets: torch.Tensor,
+                               a_group_sums: torch.Tensor, group_k: int, *, s_x0: float = 1.0, s_x1: Optional[float] = None,
+                               row_sel: Optional[torch.Tensor] = None, s_x_rows: Optional[torch.Tensor] = None,
+                               s_x_groups: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                               out_dtype: torch.dtype = torch.float16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ASYMMETRIC weight groups (``--w_groupsize`` + ``--w_asym``, ``mq_gemm_w4a8_wgroupscale_asym``): ``gemm_w4a8_wgroupscale`` with
+    acc_g + w_zero_offsets[g][n] * a_group_sums[m][g] in place of acc_g.  w_zero_offsets: int16 [K / group_k, N], 2^(b-1) - z_g[n];
+    a_group_sums: int32 [M, K / group_k] from ``act_group_rowsum`` over the same levels."""
+    _need_cuda(a, w_img, s_w_groups, w_zero_offsets, a_group_sums, row_sel, s_x_rows, s_x_groups, bias, out)
+    aptr, lda, M, K_pad = _a_args(a)
+    assert s_w_groups.dtype == torch.float32 and s_w_groups.dim() == 2 and s_w_groups.is_contiguous() and s_w_groups.shape[1] == N
+    G = s_w_groups.shape[0]
+    assert w_zero_offsets.dtype == torch.int16 and w_zero_offsets.is_contiguous() and tuple(w_zero_offsets.shape) == (G, N)
+    assert a_group_sums.dtype == torch.int32 and a_group_sums.is_contiguous() and tuple(a_group_sums.shape) == (M, G)
+    if s_x_groups is not None:
+        assert s_x_groups.dtype == torch.float32 and s_x_groups.is_contiguous() and tuple(s_x_groups.shape) == (M, G)
+    if s_x_rows is not None:
+        assert s_x_rows.dtype == torch.float32 and s_x_rows.is_contiguous() and s_x_rows.numel() == M
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=s_w_groups.device)
+    call("mq_gemm_w4a8_wgroupscale_asym", aptr, lda, w_img.data_ptr(), w_bits, M, N, K_pad, s_w_groups.data_ptr(),
+         w_zero_offsets.data_ptr(), a_group_sums.data_ptr(), G, int(group_k), float(s_x0), _second(s_x0, s_x1), _ptr(row_sel),
+         _ptr(s_x_rows), _ptr(s_x_groups), _ptr(bias), out.data_ptr(), dtype_code(out.dtype), out.stride(0), _stream())
+    return out
+
+
+@_on_device
 def gemm_w4a8_rowscale(a: torch.Tensor, w_img: torch.Tensor, w_bits: int, N: int, s_x_rows: torch.Tensor,
                        s_w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None,
                        w0: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float16,

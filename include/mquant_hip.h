@@ -721,7 +721,8 @@ int mq_rank1_add_cast(const float *y32, long M, long N, long ldy, const float *x
  * s_x(m) = s_x_rows[m] (dynamic per-token), or s_x1 where row_sel[m] else s_x0 (static, MSQ), or 1 when s_x_groups (group-wise
  * activation scales of the SAME group size, quant_utils.py:181-203; NULL otherwise: the factor is then 1 inside the sum).
  * Replaces F.linear on fake-quantized tensors (quant_utils.py:384): outputs agree with the reference to the 1e-3 of the other modes,
- * the per-group accumulators are exact.  group_k: 64 or a multiple of 128; n_groups * group_k covers K_pad up to its zero padding. */
+ * the per-group accumulators are exact.  group_k: 64 or a multiple of 128; n_groups * group_k covers K_pad up to its zero padding.
+ * M <= 16 on tiled activations (int4 weights, N % 4 == 0, 16-byte aligned s_w_groups): the streaming kernel, same bits. */
 int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
                              const float *s_w_groups, long n_groups, int group_k, float s_x0, float s_x1,
                              const uint8_t *row_sel, const float *s_x_rows, const float *s_x_groups,
@@ -736,7 +737,9 @@ int mq_gemm_w4a8_wgroupscale(const int8_t *a, long lda, const void *w, int w_bit
  *   acc'_g[m][n] = acc_g[m][n] + d_g[n] r_g[m]            (exact integers: = sum_{k in g} a[m][k] (q - z))
  *   y[m][n] = (sum_g ((float(acc'_g) * s_x_groups[m][g]) * s_w_groups[g][n])) * s_x(m) + bias[n]
  * -- mq_gemm_w4a8_wgroupscale's formula with acc' in place of acc: the same ascending group order, roundings and s_x(m) cases.  Both
- * tables are required; int8 weights: groups of at most 512 (float(acc') stays exact), larger ones are MQ_EUNSUPPORTED. */
+ * tables are required; int8 weights: groups of at most 512 (float(acc') stays exact), larger ones are MQ_EUNSUPPORTED.
+ * M <= 16 on tiled activations (int4 weights, N % 4 == 0, 16-byte aligned s_w_groups, 8-byte aligned w_zero_offsets): the streaming
+ * kernel, same bits. */
 int mq_gemm_w4a8_wgroupscale_asym(const int8_t *a, long lda, const void *w, int w_bits, long M, long N, long K_pad,
                                   const float *s_w_groups, const int16_t *w_zero_offsets, const int32_t *a_group_sums,
                                   long n_groups, int group_k, float s_x0, float s_x1, const uint8_t *row_sel,
@@ -771,6 +774,13 @@ int mq_gemm_debug_force(int tile, int splits);
 int mq_debug_act_table(int dtype, int which, const void *in_bits, const void *in2_bits, long n, void *out_fast, void *out_ref, void *stream);
 /* TEST-ONLY: the plan (tile id, split-K factor) the dispatcher takes for a shape; host arithmetic only. */
 int mq_gemm_debug_plan(long M, long N, long K_pad, int w_bits, int a_tiled, int have_workspace, int *tile, int *splits);
+/* TEST-ONLY: the tile id a weight-group GEMM call takes (61 = the streaming kernel of gemm_skinny.hip; otherwise the id of the
+ * tiled kernel, 26 = the round-1 kernel).  aligned: s_w_groups (and w_zero_offsets) meet the 16- / 8-byte alignment.
+ * x_groups: the call carries s_x_groups.  asym: mq_gemm_w4a8_wgroupscale_asym.  Host arithmetic only (no device needed); honours
+ * the calling thread's mq_gemm_debug_force: 61 = the streaming kernel wherever its requirements hold, a wave-specialised id or 26 =
+ * the tiled kernels (asymmetric groups: 26 whatever wave-specialised id is forced). */
+int mq_gemm_debug_group_plan(long M, long N, long K_pad, int w_bits, int a_tiled, int group_k, long n_groups,
+                             int x_groups, int asym, int aligned, int *tile);
 
 /* ---------------------------------------------------------------------------
  * Min/max observer reduction.  Replaces the two reductions of

@@ -188,7 +188,8 @@ enum TileId : int {
     TILE_WSD_96x128_2W = 54,
     // gemm_skinny.hip, the weight-streaming kernels for a few rows (W4, tiled activations); Plan::splits = their K slices
     TILE_SKINNY = 60,           // up to four row tiles: a wave per channel pair and slice
-    TILE_SKINNY_WG = 61,        // up to two row tiles: a workgroup per channel pair, its eight waves (and grid.y) are the slices
+    TILE_SKINNY_WG = 61,        // up to two row tiles: a workgroup per channel pair, its eight waves (and grid.y) are the slices; on a weight-group
+                                // call (one row tile): the same layout with the group fold, gemm_skinny_wgroup_kernel
 };
 constexpr bool tile_is_ws(int t) { return t >= TILE_WS_FIRST && t < TILE_WS_END; }
 constexpr bool tile_is_pp(int t) { return t >= TILE_PP_256x256 && t <= TILE_PP_256x256_DIRECT; }

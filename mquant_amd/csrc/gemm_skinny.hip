@@ -11,6 +11,8 @@
 // Two kernels: gemm_skinny_wg_kernel (TILE_SKINNY_WG, up to two row tiles) -- one workgroup per pair, its EIGHT WAVES are the K slices and
 // meet in LDS (short reductions: one launch, no workspace; long ones: a few workgroup slices on top) -- and gemm_skinny_kernel
 // (TILE_SKINNY, up to four row tiles on long reductions) -- (pairs / 4) x slices workgroups of four waves, one wave per pair and slice.
+// A third, gemm_skinny_wgroup_kernel, serves group-wise WEIGHT scales at one row tile: the eight-wave layout with the K split along
+// the groups and the fp32 group fold inside the launch (below, in front of its launcher).
 //
 // Reduction over slices of DIFFERENT workgroups: every workgroup parks its exact int32 partial sums in the split-K workspace ([slice][M][N], the
 // layout of the tiled kernels' split-K) and splitk_reduce_kernel (gemm_w4a8.hip) adds them and runs the common epilogue in a
@@ -246,6 +248,230 @@ template int launch_gemm_skinny_wg<EPI_F16>(const GemmArgs &, hipStream_t);
 template int launch_gemm_skinny_wg<EPI_BF16>(const GemmArgs &, hipStream_t);
 template int launch_gemm_skinny_wg<EPI_F32>(const GemmArgs &, hipStream_t);
 template int launch_gemm_skinny_wg<EPI_I32>(const GemmArgs &, hipStream_t);
+
+// ---- group-wise WEIGHT scales on the weight stream (mq_gemm_w4a8_wgroupscale[_asym] at M <= 16; TILE_SKINNY_WG of the group calls) ----
+// The work layout of gemm_skinny_wg_kernel -- one workgroup of eight waves per 32-channel pair, 1 KiB pieces straight into registers --
+// but the K split follows the GROUPS, because the fold is fp32 and its order is part of the result (mquant_hip.h: ascending groups, one
+// rounding per product and per sum).  Rounds of eight consecutive groups: in round r wave w owns group 8 r + w, all group_k / 64
+// k-tiles of it, accumulates it from zero and parks the exact int32 sums (acc >> 4: the levels x 16) in LDS together with the
+// group's parameters for the pair's 32 channels and the 16 rows (s_w_groups, zero offsets, activation group sums, s_x_groups: each
+// wave fetches its own group's with the weight pieces, so the fold reads LDS only).  After the round's barrier waves 0 / 1 (tile e of
+// the pair; a lane owns the output quad (m = lane & 15, n .. n + 3) of the D layout) run for the round's groups IN ASCENDING ORDER
+//     f = f + ((float(acc_g + d_g[n] r_g[m]) [* s_x_groups[m][g]]) * s_w_groups[g][n])
+// with f in registers across rounds: the order and the roundings of the tiled kernels' fold, the same bits.  Two LDS buffers: the fold
+// of round r reads buffer r & 1 while the other waves write round r + 1 into the other one; buffer r & 1 is written again behind the
+// barrier of round r + 1, which waves 0 / 1 reach after that fold.  38 KiB of LDS for every group count, no workspace, one launch.
+// A wave keeps D chunks of LU k-tiles (+ the group's parameters) in flight in a register ring: the loads of the next groups are out
+// before it waits at the barrier (plain loads survive it).  Rounds past G: a wave without a group recomputes group G - 1 (parked,
+// never folded); a zero-padding k-tile behind G group_k is never touched.
+struct WgSlot {
+    v4i acc[2][64];   // the pair's two 16-channel tiles, D layout
+    float sw[32];     // s_w_groups[g][32 ntp ..]
+    int d[32];        // w_zero_offsets[g][32 ntp ..] (asymmetric groups)
+    int rg[16];       // a_group_sums[m][g]
+    float sx[16];     // s_x_groups[m][g]
+};
+
+template <int LU>
+struct WgChunk {
+    v4i wq[LU], x[LU];
+    float sw, sx;
+    int d, rg;
+};
+
+template <int EPI, int LU, bool ASYM, bool XG>
+__global__ __launch_bounds__(512) void gemm_skinny_wgroup_kernel(GemmArgs p)
+{
+    kernarg_warm<sizeof(GemmArgs)>();
+    constexpr int D = LU >= 4 ? 2 : 3;                     // chunks in flight per wave (the register ring)
+    __shared__ WgSlot slot[2][8];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long kts = p.K_pad >> 6;
+    const long ntp = blockIdx.x;                            // one channel pair per workgroup (grid.x = n_pairs)
+    const int G = (int)p.n_groups, R = (G + 7) >> 3;
+    const int nch = p.kq, kpg = nch * LU;                   // chunks / k-tiles per group
+    const char *wp = reinterpret_cast<const char *>(p.w) + ntp * kts * 1024 + lane * 16;
+    const char *xp = reinterpret_cast<const char *>(p.a) + lane * 16;      // (M <= 16: row tile 0)
+    // the parameters a lane fetches for its wave's group: channel 32 ntp + (lane & 31), row lane & 15 -- clamped, never past N / M
+    long pn = ntp * 32 + (lane & 31);
+    if (pn >= p.N) pn = p.N - 1;
+    long pm = lane & 15;
+    if (pm >= p.M) pm = p.M - 1;
+
+    WgChunk<LU> ring[D];
+    int pr = 0, pc = 0;                                     // round / chunk of the next chunk to request
+    auto issue = [&](WgChunk<LU> &b) {
+        // past the wave's last chunk: the last one again, never used -- every call issues the same loads, so the waits in front of
+        // a chunk's first use stay COUNTED (vmcnt(n) with the younger chunks still in flight) instead of draining the ring
+        const int rr = pr < R ? pr : R - 1, cc = pr < R ? pc : nch - 1;
+        long g = (long)rr * 8 + wave;
+        if (g >= G) g = G - 1;
+        const long kt = g * kpg + (long)cc * LU;
+#pragma unroll
+        for (int u = 0; u < LU; ++u) b.wq[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(wp + (kt + u) * 1024));
+#pragma unroll
+        for (int u = 0; u < LU; ++u) b.x[u] = *reinterpret_cast<const v4i *>(xp + (kt + u) * 1024);
+        b.sw = p.sw_groups[g * p.N + pn];
+        if (ASYM) {
+            b.d = (int)p.wd_groups[g * p.N + pn];
+            b.rg = p.a_gsums[pm * G + g];
+        }
+        if (XG) b.sx = p.sx_groups[pm * G + g];
+        if (++pc == nch) { pc = 0; ++pr; }
+    };
+    v4i acc[2] = {v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}};
+    auto mac = [&](const v4i wq, const v4i x) {
+        const v4i w0 = v4i{(wq[0] << 4) & (int)0xF0F0F0F0, wq[0] & (int)0xF0F0F0F0, (wq[1] << 4) & (int)0xF0F0F0F0, wq[1] & (int)0xF0F0F0F0};
+        const v4i w1 = v4i{(wq[2] << 4) & (int)0xF0F0F0F0, wq[2] & (int)0xF0F0F0F0, (wq[3] << 4) & (int)0xF0F0F0F0, wq[3] & (int)0xF0F0F0F0};
+        acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, x, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, x, acc[1], 0, 0, 0);
+    };
+    // D layout: column (lane & 15) = activation row, register q = channel 16 e + 4 (lane >> 4) + q of the pair's tile e = wave (0 / 1)
+    const int ml = lane & 15, nq = (lane >> 4) * 4;
+    float f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto fold = [&](int r) {
+        const WgSlot *sb = slot[r & 1];
+        const int ng = G - 8 * r < 8 ? G - 8 * r : 8;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            if (w >= ng) break;
+            const v4i a = sb[w].acc[wave][lane];
+            const v4f sw = *reinterpret_cast<const v4f *>(&sb[w].sw[wave * 16 + nq]);
+            const v4i d = *reinterpret_cast<const v4i *>(&sb[w].d[wave * 16 + nq]);
+            const int rg = sb[w].rg[ml];
+            const float sx = sb[w].sx[ml];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int v = a[q];
+                if (ASYM) v += d[q] * rg;                   // acc' = acc + d r: exact integers
+                float t = (float)v;
+                if (XG) t = t * sx;
+                t = t * sw[q];
+                f[q] = f[q] + t;
+            }
+        }
+    };
+
+    // the epilogue's row scale and bias, requested in front of the stream (clamped, unconditional loads: no wait is left at the end)
+    float sxr = p.sx0, bv[4];                               // (s_x0 = 1.0 with s_x_groups: exact)
+    {
+        const long mc = ml < p.M ? ml : p.M - 1;
+        if (p.sx_vec) sxr = p.sx_vec[mc];
+        else if (p.row_sel && p.row_sel[mc]) sxr = p.sx1;
+        const float *bp = p.bias ? p.bias : p.sw_groups;    // (a table of N floats either way)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long nn = (ntp * 2 + (wave & 1)) * 16 + nq + q;
+            bv[q] = bp[nn < p.N ? nn : p.N - 1];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < D - 1; ++j) issue(ring[j]);
+    const int total = R * nch;
+    int r = 0, c = 0;
+    for (int i0 = 0; i0 < total; i0 += D) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            if (i0 + j >= total) break;
+            issue(ring[(j + D - 1) % D]);
+#pragma unroll
+            for (int u = 0; u < LU; ++u) mac(ring[j].wq[u], ring[j].x[u]);
+            if (++c < nch) continue;
+            c = 0;
+            WgSlot &s = slot[r & 1][wave];
+            s.acc[0][lane] = acc[0] >> 4;                   // (levels x 16: the shift is exact)
+            s.acc[1][lane] = acc[1] >> 4;
+            acc[0] = acc[1] = v4i{0, 0, 0, 0};
+            if (lane < 32) {
+                s.sw[lane] = ring[j].sw;
+                s.d[lane] = ASYM ? ring[j].d : 0;
+            }
+            if (lane < 16) {
+                s.rg[lane] = ASYM ? ring[j].rg : 0;
+                s.sx[lane] = XG ? ring[j].sx : 1.0f;
+            }
+            __syncthreads();
+            if (wave < 2) fold(r);
+            ++r;
+        }
+    }
+    if (wave >= 2) return;
+    const long m = ml, n = (ntp * 2 + wave) * 16 + nq;
+    if (m >= p.M || n >= p.N) return;
+    float y[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float t = f[q] * sxr;
+        if (p.bias) t = t + bv[q];
+        y[q] = t;
+    }
+    constexpr int ESZ = EPI == EPI_F32 ? 4 : 2;
+    const bool full = (n + 4 <= p.N) && (p.ldo % 4 == 0) && (reinterpret_cast<uintptr_t>(p.out) % (4 * ESZ) == 0);
+    if (EPI == EPI_F32) {
+        float *o = reinterpret_cast<float *>(p.out) + m * p.ldo + n;
+        if (full) {
+            store_out(reinterpret_cast<v4f *>(o), v4f{y[0], y[1], y[2], y[3]});
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (n + q < p.N) o[q] = y[q];
+        }
+    } else {
+        unsigned short h[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) h[q] = (EPI == EPI_F16) ? f32_to_f16_bits(y[q]) : f32_to_bf16_bits(y[q]);
+        unsigned short *o = reinterpret_cast<unsigned short *>(p.out) + m * p.ldo + n;
+        if (full) {
+            store_out(reinterpret_cast<v4us *>(o), v4us{h[0], h[1], h[2], h[3]});
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (n + q < p.N) o[q] = h[q];
+        }
+    }
+}
+
+// What the kernel above needs of a group call (the plan asks the same question before it answers TILE_SKINNY_WG: gemm_w4a8.hip).
+bool skinny_wgroup_ok(long M, long N, int w_bits, bool a_tiled, int group_k, long n_groups, bool aligned)
+{
+    return w_bits == 4 && a_tiled && M >= 1 && M <= 16 && N % 4 == 0 && aligned && ceil_div(N, 32) <= 0x7fffffffL
+           && (group_k == 64 || (group_k > 0 && group_k % 128 == 0)) && n_groups >= 1 && n_groups <= 0x7ffffff0L;
+}
+
+template <int EPI>
+int launch_gemm_skinny_wgroup(const GemmArgs &p, int w_bits, hipStream_t st)
+{
+    static_assert(EPI != EPI_I32, "the group fold has floating-point outputs only");
+    const bool aligned = p.sw_groups && ((uintptr_t)p.sw_groups) % 16 == 0 && ((uintptr_t)p.wd_groups) % 8 == 0;
+    if (!skinny_wgroup_ok(p.M, p.N, w_bits, p.a_tiled != 0, p.group_k, p.n_groups, aligned) || p.shift_groups || (p.wd_groups != nullptr) != (p.a_gsums != nullptr)
+        || (long)p.group_k * p.n_groups > p.K_pad)
+        return fail(MQ_EINVAL, "gemm_skinny_wgroup: needs int4 weights, tiled activations, 1 <= M <= 16, N %% 4 == 0, s_w_groups 16-byte and w_zero_offsets 8-byte aligned");
+    GemmArgs g = p;
+    const int kpg = p.group_k / 64;
+    const int lu = kpg == 1 ? 1 : (kpg % 4 == 0 ? 4 : 2);
+    g.kq = kpg / lu;                                         // chunks of `lu` k-tiles per group
+    g.kr = 0;
+    const dim3 grid((unsigned)p.n_pairs);
+    auto go = [&](auto lu_c) {
+        constexpr int LU = decltype(lu_c)::value;
+        if (p.wd_groups) {
+            if (p.sx_groups) hipLaunchKernelGGL((gemm_skinny_wgroup_kernel<EPI, LU, true, true>), grid, dim3(512), 0, st, g);
+            else hipLaunchKernelGGL((gemm_skinny_wgroup_kernel<EPI, LU, true, false>), grid, dim3(512), 0, st, g);
+        } else {
+            if (p.sx_groups) hipLaunchKernelGGL((gemm_skinny_wgroup_kernel<EPI, LU, false, true>), grid, dim3(512), 0, st, g);
+            else hipLaunchKernelGGL((gemm_skinny_wgroup_kernel<EPI, LU, false, false>), grid, dim3(512), 0, st, g);
+        }
+    };
+    if (lu == 1) go(std::integral_constant<int, 1>{});
+    else if (lu == 2) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 4>{});
+    return check_launch("gemm_skinny_wgroup");
+}
+
+template int launch_gemm_skinny_wgroup<EPI_F16>(const GemmArgs &, int, hipStream_t);
+template int launch_gemm_skinny_wgroup<EPI_BF16>(const GemmArgs &, int, hipStream_t);
+template int launch_gemm_skinny_wgroup<EPI_F32>(const GemmArgs &, int, hipStream_t);
 
 // workgroup slices of the eight-wave kernel on a long reduction: ~2 workgroups per CU, at least 32 k-tiles (four per wave) each
 int skinny_wg_slices(long M, long N, long K_pad, size_t ws_bytes)

@@ -42,6 +42,9 @@ int skinny_slices(long M, long N, long K_pad, size_t ws_bytes);
 int skinny_wg_slices(long M, long N, long K_pad, size_t ws_bytes);
 template <int EPI>
 int launch_gemm_skinny_wg(const GemmArgs &p, hipStream_t st);          // gemm_skinny.hip (M <= 16, K <= 4096: the K slices are a workgroup's waves; TILE_SKINNY_WG)
+template <int EPI>
+int launch_gemm_skinny_wgroup(const GemmArgs &p, int w_bits, hipStream_t st);   // gemm_skinny.hip (weight-group scales at M <= 16: the fold on the weight stream; TILE_SKINNY_WG of the group calls)
+bool skinny_wgroup_ok(long M, long N, int w_bits, bool a_tiled, int group_k, long n_groups, bool aligned);
 
 // GROUPED (--a_groupsize): the int32 accumulators of one activation group (64 or a multiple of 128 k) are scaled by
 // the group's activation scale of their row and added to fp32 accumulators in ascending group order; the epilogue
@@ -700,6 +703,35 @@ static int dispatch_tile(const GemmArgs &p, int tile, hipStream_t st)
 static thread_local int g_force_tile = -1, g_force_splits = 0;
 thread_local int g_gemm_force_xm = 0;
 
+// The kernel a WEIGHT-GROUP call (mq_gemm_w4a8_wgroupscale[_asym]) takes, as a tile id: TILE_SKINNY_WG = the streaming kernel with the group
+// fold (gemm_skinny.hip), a wave-specialised id = the fold in gemm_ws.hip (symmetric groups), TILE_SYM_128x128 = the round-1 kernel (asymmetric
+// groups, row-major activations, unaligned tables).  Host arithmetic; the dispatcher and mq_gemm_debug_group_plan both call THIS function.
+// force_tile (mq_gemm_debug_force): TILE_SKINNY_WG = the streaming kernel wherever its requirements hold (ignored elsewhere, like every forced
+// tile outside a mode's set); a wave-specialised id or TILE_SYM_128x128 keeps the tiled kernels, which is how the A/B runs address them.
+// Where the streaming kernel was MEASURED faster than the tiled kernel of the same call (tools/decode_wgroup_bench.py,
+// profiles/decode_wgroup_gemm_bench.txt; cold weights, M = 1 / 8 / 16, symmetric and asymmetric): every class that was run --
+// groups of 64, 128 and 256, 2 ... 312 of them, N = 512 ... 37888, K = 256 ... 19968 -- at 0.19 ... 0.80 of the wave-specialised fold
+// (symmetric) and 0.03 ... 0.34 of the round-1 kernel (asymmetric), the gap always many times the spread of three repetitions.  A single
+// group and groups above 256 were not measured: they keep the tiled kernels (mq_gemm_debug_force(61) still reaches the kernel there).
+static bool wgroup_stream_gains(long M, long N, long K_pad, int group_k, long n_groups, bool asym)
+{
+    (void)N; (void)K_pad; (void)asym;
+    return M <= 16 && n_groups >= 2 && group_k <= 256;
+}
+
+static int wgroup_plan_tile(long M, long N, long K_pad, int w_bits, bool a_tiled, int group_k, long n_groups, bool x_groups, bool asym, bool aligned,
+                            int force_tile)
+{
+    (void)x_groups;
+    const bool stream_ok = skinny_wgroup_ok(M, N, w_bits, a_tiled, group_k, n_groups, aligned) && (long)group_k * n_groups <= K_pad;
+    const bool keep_tiled = force_tile == TILE_SYM_128x128 || tile_is_ws(force_tile);
+    if (stream_ok && (force_tile == TILE_SKINNY_WG || (!keep_tiled && wgroup_stream_gains(M, N, K_pad, group_k, n_groups, asym)))) return TILE_SKINNY_WG;
+    if (asym) return TILE_SYM_128x128;
+    if (a_tiled && N % 4 == 0 && aligned && force_tile != TILE_SYM_128x128)
+        return make_plan(M, N, K_pad, false, 0, force_tile, 0, w_bits == 4, true, PlanMode::WS_ONLY).tile;
+    return TILE_SYM_128x128;
+}
+
 // One call of the dispatcher: what an entry point was given, by name.  A member an entry point does not set keeps the value that turns its
 // epilogue term off.
 struct GemmCall {
@@ -796,6 +828,16 @@ static int gemm_common(const GemmCall &c)
         p.shift_groups = c.shift_groups; p.wsum_groups = c.wsum_groups;
         p.splits = 1; p.partial = nullptr;
         p.par_ok = al16(c.s_w) && al16(c.bias) && al16(c.w0);
+        // weight groups: ONE host function names the kernel (wgroup_plan_tile; mq_gemm_debug_group_plan reports the same answer)
+        const bool wg_aligned = ((uintptr_t)c.sw_groups) % 16 == 0 && ((uintptr_t)c.wd_groups) % 8 == 0;
+        const int wg_tile = c.sw_groups ? wgroup_plan_tile(M, N, K_pad, c.w_bits, a_tiled, c.group_k, c.n_groups, c.sx_groups != nullptr, c.wd_groups != nullptr,
+                                                           wg_aligned, g_force_tile)
+                                        : -1;
+        if (wg_tile == TILE_SKINNY_WG) {
+            // a few rows on tiled activations: the fold rides on the weight stream (gemm_skinny.hip), symmetric and asymmetric groups, same bits
+            p.wd_groups = c.wd_groups; p.a_gsums = c.a_gsums;
+            return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) { return launch_gemm_skinny_wgroup<decltype(e)::value>(p, decltype(wb)::value, st); });
+        }
         if (c.wd_groups) {
             // asymmetric weight groups: the round-1 kernel, whose fold CONVERTS the group's integer -- exact for every group size the
             // entry point lets through.  The wave-specialised fold reads a group's sum out of the magic bias without a conversion, which
@@ -807,14 +849,14 @@ static int gemm_common(const GemmCall &c)
                 return launch_gemm<128, 128, 2, 4, 3, decltype(wb)::value, decltype(e)::value, 1, true, true>(p, st);
             });
         }
-        if (a_tiled && !c.shift_groups && (!c.sw_groups || (N % 4 == 0 && ((uintptr_t)c.sw_groups) % 16 == 0)) && g_force_tile != TILE_SYM_128x128) {
+        if (c.sw_groups ? wg_tile != TILE_SYM_128x128 : (a_tiled && !c.shift_groups && g_force_tile != TILE_SYM_128x128)) {
             // symmetric group scales (weights, activations or both) on tiled activations, groups of 64 or of whole k-steps: the fold rides in the
             // wave-specialised 16x16x64 kernels (weight groups of 128: 1.8-2.4 x the per-channel GEMM of the shape, profiles/r5_group_gemm_ws_fold.txt,
             // against 5.8-8.8 x on the round-1 kernel below, profiles/r5_group_gemm_round1_kernel.txt);
             // mq_gemm_debug_force(26) keeps the round-1 kernel for A/B
-            const Plan gpl = make_plan(M, N, K_pad, false, 0, g_force_tile, 0, c.w_bits == 4, true, PlanMode::WS_ONLY);
+            const int gtile = c.sw_groups ? wg_tile : make_plan(M, N, K_pad, false, 0, g_force_tile, 0, c.w_bits == 4, true, PlanMode::WS_ONLY).tile;
             return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) {
-                return dispatch_ws_wgroup<decltype(wb)::value, decltype(e)::value>(p, gpl.tile, st);
+                return dispatch_ws_wgroup<decltype(wb)::value, decltype(e)::value>(p, gtile, st);
             });
         }
         return with_bits_epi<false>(c.w_bits, c.epi, [&](auto wb, auto e) {
@@ -882,6 +924,18 @@ extern "C" int mq_gemm_debug_plan(long M, long N, long K_pad, int w_bits, int a_
     const mq::Plan pl = mq::make_plan(M, N, K_pad, have_workspace != 0, have_workspace ? ((size_t)1 << 40) : 0, -1, 0, w_bits == 4, a_tiled != 0);
     *tile = pl.tile;
     *splits = pl.splits;
+    return MQ_OK;
+}
+
+// TEST-ONLY: the tile id a weight-group call takes (wgroup_plan_tile under the calling thread's mq_gemm_debug_force; no device needed).
+extern "C" int mq_gemm_debug_group_plan(long M, long N, long K_pad, int w_bits, int a_tiled, int group_k, long n_groups, int x_groups, int asym,
+                                        int aligned, int *tile)
+{
+    if (!tile || M < 1 || N < 1 || K_pad <= 0 || K_pad % 128 || (w_bits != 4 && w_bits != 8) || n_groups < 1
+        || !(group_k == 64 || (group_k > 0 && group_k % 128 == 0)))
+        return mq::fail(MQ_EINVAL, "mq_gemm_debug_group_plan: bad arguments");
+    if (const int rc = mq::check_groups_cover(__func__, n_groups, group_k, K_pad)) return rc;
+    *tile = mq::wgroup_plan_tile(M, N, K_pad, w_bits, a_tiled != 0, group_k, n_groups, x_groups != 0, asym != 0, aligned != 0, mq::g_force_tile);
     return MQ_OK;
 }
 

@@ -985,6 +985,18 @@ def gemm_debug_force(tile: int = -1, splits: int = 0) -> None:
     call("mq_gemm_debug_force", tile, splits)
 
 
+def gemm_group_plan(M: int, N: int, K_pad: int, group_k: int, n_groups: Optional[int] = None, *, w_bits: int = 4, a_tiled: bool = True,
+                    x_groups: bool = False, asym: bool = False, aligned: bool = True) -> int:
+    """The tile id a weight-group GEMM call takes (``mq_gemm_debug_group_plan``: host arithmetic, no device needed, honours
+    ``gemm_debug_force``): 61 = the streaming kernel of gemm_skinny.hip, otherwise the tiled kernel's id (26 = the round-1 kernel)."""
+    import ctypes
+    tile = ctypes.c_int(-1)
+    G = K_pad // group_k if n_groups is None else n_groups
+    call("mq_gemm_debug_group_plan", M, N, K_pad, w_bits, int(a_tiled), int(group_k), int(G), int(x_groups), int(asym), int(aligned),
+         ctypes.cast(ctypes.byref(tile), ctypes.c_void_p))
+    return tile.value
+
+
 @_on_device
 def gemm_w4a8(a: torch.Tensor, w_img: torch.Tensor, w_bits: int, N: int, s_x0: float,
               s_w: torch.Tensor, *, s_x1: Optional[float] = None,
